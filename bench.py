@@ -3,6 +3,7 @@
 [+ gradient all-reduce]) of BertForVLPreTraining on synthetic ConceptualCaptions-shaped batches.
 
   python bench.py --gpus N --steps K --warmup W          (N > 1: launched through torch.distributed.run)
+  python bench.py ... --dump-outputs DIR                 (+ what the last timed step computed, as DIR/*.npy: dump_outputs)
 
 Prints ONE JSON line (rank 0): image-text pairs/s over all GPUs, the MFMA roofline of the step and of the
 GEMM kernel family (timed live with HIP events on the launch stream), and a CPU baseline (the fp32 oracle
@@ -46,7 +47,39 @@ def parse():
     ap.add_argument("--no-dropout", action="store_true", help="DIAGNOSTIC, not the BASELINE workload (the line says so): every dropout probability 0 -- what the counter-based mask generation costs the step")
     ap.add_argument("--no-optimizer", action="store_true", help="DIAGNOSTIC, not the BASELINE workload (the line says so): forward + backward only -- what clip + AdamW add to the step beyond what the next forward hides")
     ap.add_argument("--dump-ops", default=None, help="write the per-op timing table of the profiled steps to this file")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy (see dump_outputs)")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
+
+
+DUMP_BYTES = 64 << 20        # --dump-outputs: the whole dump stays under this
+DUMP_PER_PARAM = 4096        # elements sampled from one parameter (all of a smaller one)
+
+
+def dump_outputs(d, model, losses, seed=1234):
+    """--dump-outputs DIR: what the last timed step computed, as float32 .npy files, for comparing two builds output for output.
+      losses.npy         [3]  masked-LM, masked-region and image-text-match losses the step returned
+      params_sample.npy       the parameters after that step's AdamW update, sampled
+      grads_sample.npy        the gradients that step's backward produced (before the clip, which AdamW applies), same positions
+    The sample takes every element of a parameter of up to DUMP_PER_PARAM elements and DUMP_PER_PARAM seeded positions of a larger one,
+    in named_parameters() order: the positions depend on the config alone, not on the arena layout."""
+    import numpy as np
+    arena = model.materialize()
+    per = max(1, min(DUMP_PER_PARAM, DUMP_BYTES // (2 * 4) // len(arena.names)))
+    rng = np.random.default_rng(seed)
+    idx = []
+    for name in arena.names:
+        n = int(np.prod(arena.shape[name], dtype=np.int64))
+        pos = np.arange(n) if n <= per else np.sort(rng.choice(n, per, replace=False))
+        idx.append(arena.offset[name] + pos)
+    idx = torch.from_numpy(np.concatenate(idx)).to(arena.master.device)
+    torch.cuda.synchronize()                 # the pipelined AdamW runs on a stream of its own
+    out = {"losses": torch.cat([x.detach().reshape(-1) for x in losses]), "params_sample": arena.master[idx], "grads_sample": arena.grad[idx]}
+    os.makedirs(d, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(d, k + ".npy"), v.float().cpu().numpy())
 
 
 def gemm_flops(eng, plan):
@@ -212,7 +245,8 @@ def dry_run(a, world, rank):
         dist.init_process_group("gloo")
     buf = torch.ones(1024)
 
-    def step():
+    def step():                 # buf counts the steps run (every rank adds 1, the mean over ranks keeps the count)
+        buf.add_(1.0)
         if world > 1:
             dist.all_reduce(buf)
             buf.mul_(1.0 / world)
@@ -234,6 +268,10 @@ def dry_run(a, world, rank):
         elapsed = float(t)
     out, _, _ = result_line(a, world, elapsed, t_issue, {"dry_run": "harness rehearsal on CPU over gloo: no model step ran, the value means nothing"})
     if rank == 0:
+        if a.dump_outputs:
+            import numpy as np
+            os.makedirs(a.dump_outputs, exist_ok=True)
+            np.save(os.path.join(a.dump_outputs, "allreduce_buf.npy"), buf.numpy())
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()
@@ -322,6 +360,8 @@ def main():
         t = torch.tensor([elapsed], device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t)
+    if a.dump_outputs and rank == 0:         # before the untimed steps below move the weights on
+        dump_outputs(a.dump_outputs, model, losses)
     # Host WORK per step: the same step issued into an EMPTY queue (synchronise first), on every rank alike.  `host_issue_ms_per_step` above
     # is the wall time of the issuing loop, which the bounded HIP queues throttle to the GPU's pace once they are full -- it approaches
     # ms_per_step by construction and says nothing about host cost; this figure does.

@@ -286,8 +286,9 @@ typedef struct vk_embed_args {
 } vk_embed_args;
 int vk_embed_sum_fwd(const vk_embed_args* a, vk_stream_t s);
 /* Backward of the lookups (autograd of nn.Embedding): dword / dtype (and dpos when pos_ids != NULL) are
- * ACCUMULATED with atomics (caller zeroes them, or lets the tied LM-decoder wgrad write dword first);
- * with implicit positions dpos rows [0, T) are overwritten. */
+ * ACCUMULATED, every table row once and in a fixed order: the same bits on every run (caller zeroes them, or lets the
+ * tied LM-decoder wgrad write dword first); with implicit positions dpos rows [0, T) are overwritten.
+ * work: vk_embed_bwd_workspace_bytes(M, H, V, P, pos_ids && dpos) bytes of device memory, 256-byte aligned. */
 typedef struct vk_embed_bwd_args {
     const void* dz;           /* bf16 [M, H] */
     const int64_t* ids;
@@ -298,7 +299,9 @@ typedef struct vk_embed_bwd_args {
     float* dtype;             /* may be NULL */
     int32_t M, T, H, n_types;
     int32_t V, P;
+    void* work;               /* workspace, see above */
 } vk_embed_bwd_args;
+int64_t vk_embed_bwd_workspace_bytes(int M, int H, int V, int P, int has_pos);
 int vk_embed_sum_bwd(const vk_embed_bwd_args* a, vk_stream_t s);
 
 /* Box-location linear (nn.Linear(num_locs=5, H), volta/embeddings.py:135,141,157,164,420,450): fp32 in,

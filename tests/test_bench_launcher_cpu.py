@@ -38,3 +38,19 @@ def test_single_rank_needs_no_launcher():
 def test_world_size_mismatch_fails_loudly():
     r = _run(["--gpus", "4", "--steps", "1", "--warmup", "0"], extra_env={"WORLD_SIZE": "2", "RANK": "0", "LOCAL_RANK": "0"})
     assert r.returncode != 0 and "WORLD_SIZE=2" in (r.stderr + r.stdout)
+
+
+def test_steps_sets_the_timed_steps_and_dump_outputs_writes_the_last_one(tmp_path):
+    import numpy as np
+    d = tmp_path / "out"
+    r = _run(["--steps", "4", "--warmup", "1", "--dump-outputs", str(d)])
+    assert r.returncode == 0, r.stderr[-2000:]
+    out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
+    assert out["steps"] == 4 and out["ms_per_step"] > 0
+    buf = np.load(d / "allreduce_buf.npy")
+    assert buf.dtype == np.float32 and buf.shape == (1024,) and (buf == 1 + 1 + 4).all()      # initial 1, one warm-up step, four timed steps
+
+
+def test_zero_steps_is_refused():
+    r = _run(["--steps", "0", "--warmup", "0"])
+    assert r.returncode != 0 and "--steps" in r.stderr

@@ -43,7 +43,7 @@ def test_ddp_world1_matches_plain_backward():
         assert covered[0][0] == 0 and sum(hi - lo for lo, hi in covered) >= sum(p.numel() for p in model.parameters())
         for k, p in model.named_parameters():
             if "embeddings.word_embeddings" in k or "token_type_embeddings" in k:
-                # scatter-added with fp32 atomics: summation order (last bits) varies from run to run
+                # table rows: checked to a last-bit tolerance
                 assert torch.allclose(p.grad, plain[k], rtol=1e-4, atol=1e-7), k
             else:
                 assert torch.equal(p.grad, plain[k]), k

@@ -83,7 +83,7 @@ def _worker(rank, world, port, shared_gpu=False):
             if mode == "zero1":
                 assert ddp.reducer.sharded, "no bucket was sharded"
             m2.__dict__["_ddp"] = None
-        # (between the two RUNS a last-bit tolerance: the backward's embedding and loss row sums are accumulated with float atomics, so
+        # (between the two RUNS a last-bit tolerance: the backward's loss row sums are accumulated with float atomics, so
         # two backward passes over the same batch already differ in the last bit (tests/test_fullsize_gpu.py), and with more than two
         # ranks the collectives add a slot's contributions in different ring orders.  Within a run the replicas are bit-identical.)
         for a, b2, what in zip(runs["allreduce"][:4], runs["zero1"][:4], ("master weights", "bf16 copies", "exp_avg", "exp_avg_sq")):

@@ -95,7 +95,7 @@ class EmbedArgs(C.Structure):
 
 class EmbedBwdArgs(C.Structure):
     _fields_ = [("dz", c_p), ("ids", c_p), ("type_ids", c_p), ("pos_ids", c_p), ("dword", c_p), ("dpos", c_p),
-                ("dtype", c_p), ("M", i32), ("T", i32), ("H", i32), ("n_types", i32), ("V", i32), ("P", i32)]
+                ("dtype", c_p), ("M", i32), ("T", i32), ("H", i32), ("n_types", i32), ("V", i32), ("P", i32), ("work", c_p)]
 
 
 class XentArgs(C.Structure):
@@ -191,6 +191,7 @@ _sig("vk_ln_bwd_partial_rows", C.c_int, C.c_int)
 _sig("vk_ln_bwd", C.c_int, C.POINTER(LnBwdArgs), c_p)
 _sig("vk_embed_sum_fwd", C.c_int, C.POINTER(EmbedArgs), c_p)
 _sig("vk_embed_sum_bwd", C.c_int, C.POINTER(EmbedBwdArgs), c_p)
+_sig("vk_embed_bwd_workspace_bytes", C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int)
 _sig("vk_rows32", C.c_int, C.c_int)
 _sig("vk_loc_linear_fwd", C.c_int, c_p, c_p, c_p, c_p, C.c_int, C.c_int, C.c_int, c_p)
 _sig("vk_loc_linear_bwd", C.c_int, c_p, c_p, c_p, c_p, c_p, C.c_int, C.c_int, C.c_int, c_p)
@@ -268,7 +269,7 @@ _sig("vk_side_stream", c_p, c_p)
 
 EXPORTS = ["vk_version", "vk_device_arch", "vk_last_error", "vk_set_seed", "vk_cast_f32_bf16", "vk_gemm_grouped", "vk_gemm_grouped_ex", "vk_gemm_chain", "vk_gemm_split_workspace_bytes", "vk_gemm_fp8_grouped", "vk_quant_rows_fp8", "vk_cast_bf16_fp8",
            "vk_ln_fwd", "vk_ln_fwd_pair", "vk_ln_bwd_partial_rows", "vk_ln_bwd", "vk_ln_bwd_pair", "vk_ln_bwd_finalize", "vk_gated_attn_fwd", "vk_gated_attn_bwd", "vk_gated_attn_lds_bytes",
-           "vk_embed_sum_fwd", "vk_embed_sum_bwd", "vk_rows32", "vk_loc_linear_fwd", "vk_loc_linear_bwd",
+           "vk_embed_sum_fwd", "vk_embed_sum_bwd", "vk_embed_bwd_workspace_bytes", "vk_rows32", "vk_loc_linear_fwd", "vk_loc_linear_bwd",
            "vk_add_dropout", "vk_colsum_bf16", "vk_vlbert_prep_fwd", "vk_vlbert_maskgrad", "vk_rowgroup_sum_bf16",
            "vk_relu_bwd_bf16", "vk_copy_async", "vk_select_rows", "vk_gather_rows", "vk_scatter_rows_add", "vk_xent_fwd",
            "vk_xent_bwd", "vk_kl_fwd", "vk_kl_bwd", "vk_loss_finalize", "vk_pool_mul_fwd", "vk_pool_mul_bwd",

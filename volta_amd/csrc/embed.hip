@@ -1,12 +1,13 @@
 // Embedding-side kernels (HBM-bound, one wave per row, 8/16-byte accesses):
 //   * text embedding sum  word[ids] + pos[t] + type[seg] (+ extra)        volta/embeddings.py:55-66
-//   * its backward: scatter-add into the three tables
+//   * its backward: sums into the three tables, in a fixed order (the same bits on every run)
 //   * the 5-wide box-location linear and its backward                     volta/embeddings.py:135,141
 //   * y = dropout((a + b) * scale) and its backward (LXMERT image embedding, embeddings.py:169-170)
 //   * column sums of a bf16 matrix (gradient of a broadcast row vector)
 #include "common.h"
 #include "../../include/volta_hip.h"
 #include "util.h"
+#include <climits>
 
 namespace vk {
 
@@ -42,13 +43,27 @@ __global__ __launch_bounds__(256) void embed_sum_fwd_kernel(vk_embed_args a) {
     }
 }
 
-// Word table: float atomics, but only ONE per workgroup, column and distinct id.  A workgroup takes 32 rows of the SAME position t (samples
-// b0 .. b0+31: row = b * T + t), because that is where ids repeat -- [CLS] at t = 0 and [SEP] at the caption's end in every sample, [MASK] on
-// 15 % of the rest -- and the first row of every id inside the workgroup sums its duplicates before it touches the table.  (One atomic per
-// row and column made 256-700 of them queue on the same address for the three hot ids: 110 us for 5120 x 768, on the critical path of the step.)
-// Type table (<= 4 rows, every row of the batch hits them): per-workgroup partial sums first, one atomic per workgroup and column afterwards.
+// Backward of the lookups in two launches, deterministic (float atomics from many workgroups would add in arrival order, and AdamW
+// carries that last-bit noise into the weights):
+//   embed_scatter_kernel: a workgroup takes 32 rows of the SAME position t (samples b0 .. b0+31: row = b * T + t), because that is where
+//     ids repeat -- [CLS] at t = 0 and [SEP] at the caption's end in every sample, [MASK] on 15 % of the rest -- and the first row of every
+//     id inside the workgroup sums its duplicates into a workspace slot (slot = 32 * workgroup + that row's index in it).  The slot's key
+//     is recorded and the key's lowest slot elected with an integer atomicMin (order-independent).  Type table (<= 4 rows): per-workgroup
+//     sums into the workspace.  (One atomic per row and column made 256-700 of them queue on the same address for the three hot ids.)
+//   embed_combine_kernel: the elected slot of every key adds the key's slots in slot order, four waves over fixed slot ranges summed in
+//     wave order, and writes the table row once; the type rows add the per-workgroup sums in the same fixed way.
+struct EmbWs {
+    float* Pw;       // [S, H] word-table partial of a slot
+    float* Pp;       // [S, H] position-table partial (explicit positions), or NULL
+    float* Q;        // [S / 32, 4, H] per-workgroup type-table sums
+    int* kw;         // [S] key of a word slot, -1 when the slot holds none
+    int* kp;         // [S] key of a position slot, or NULL
+    int* ow;         // [V] lowest slot of a word id (INT_MAX: none)
+    int* op;         // [P] lowest slot of a position id, or NULL
+};
+
 template <int NCH>
-__global__ __launch_bounds__(256) void embed_scatter_kernel(vk_embed_bwd_args a) {
+__global__ __launch_bounds__(256) void embed_scatter_kernel(vk_embed_bwd_args a, EmbWs w) {
     __shared__ float red[4][4][NCH * 256];
     __shared__ int64_t id_s[32];
     __shared__ int ty_s[32], row_s[32];
@@ -65,6 +80,21 @@ __global__ __launch_bounds__(256) void embed_scatter_kernel(vk_embed_bwd_args a)
         ps_s[threadIdx.x] = (row >= 0 && a.pos_ids) ? clampi(a.pos_ids[row], a.P) : -1;
     }
     __syncthreads();
+    if (threadIdx.x < 32) {
+        const int tid = threadIdx.x, slot = blockIdx.x * 32 + tid;
+        const int64_t id = id_s[tid];
+        bool f = row_s[tid] >= 0;                              // the first row of its id in this workgroup
+        for (int q = 0; q < tid; ++q) f &= id_s[q] != id;
+        w.kw[slot] = f ? (int)id : -1;
+        if (f) atomicMin(w.ow + id, slot);
+        if (w.kp) {
+            const int64_t ps = ps_s[tid];
+            bool fp = ps >= 0;
+            for (int q = 0; q < tid; ++q) fp &= ps_s[q] != ps;
+            w.kp[slot] = fp ? (int)ps : -1;
+            if (fp) atomicMin(w.op + ps, slot);
+        }
+    }
     float ta[4][NCH][4];
 #pragma unroll
     for (int k = 0; k < 4; ++k)
@@ -122,8 +152,7 @@ __global__ __launch_bounds__(256) void embed_scatter_kernel(vk_embed_bwd_args a)
             for (int j = 0; j < NCH; ++j) {
                 const int c = j * 256 + lane * 4;
                 if (c < a.H) {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) atomicAdd(a.dpos + (size_t)ps * a.H + c + r, pacc[j][r]);
+                    *(f32x4*)(w.Pp + (size_t)(blockIdx.x * 32 + r0) * a.H + c) = f32x4{pacc[j][0], pacc[j][1], pacc[j][2], pacc[j][3]};
                 }
             }
         }
@@ -170,8 +199,7 @@ __global__ __launch_bounds__(256) void embed_scatter_kernel(vk_embed_bwd_args a)
         for (int j = 0; j < NCH; ++j) {
             const int c = j * 256 + lane * 4;
             if (c < a.H) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) atomicAdd(a.dword + (size_t)id * a.H + c + r, acc[j][r]);
+                *(f32x4*)(w.Pw + (size_t)(blockIdx.x * 32 + r0) * a.H + c) = f32x4{acc[j][0], acc[j][1], acc[j][2], acc[j][3]};
             }
         }
     }
@@ -186,8 +214,91 @@ __global__ __launch_bounds__(256) void embed_scatter_kernel(vk_embed_bwd_args a)
     for (int i = threadIdx.x; i < a.n_types * a.H; i += 256) {
         const int k = i / a.H, c = i - k * a.H;
         const float s = red[0][k][c] + red[1][k][c] + red[2][k][c] + red[3][k][c];
-        if (s != 0.f) atomicAdd(a.dtype + (size_t)k * a.H + c, s);
+        w.Q[((size_t)blockIdx.x * 4 + k) * a.H + c] = s;
     }
+}
+
+template <int NCH>
+__global__ __launch_bounds__(256) void embed_combine_kernel(vk_embed_bwd_args a, EmbWs w, int S) {
+    __shared__ float red[4 * 1024];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int s = blockIdx.x;
+    if (s >= S) {                                              // type table: columns [64 cb, 64 cb + 64), workgroups g = 8 wave .. in order
+        if (blockIdx.y != 0) return;
+        const int nwg = S / 32, c = (s - S) * 64 + lane;
+        float t[4] = {0.f, 0.f, 0.f, 0.f};
+        if (c < a.H) {
+            for (int g0 = wave * 8; g0 < nwg; g0 += 32) {
+                float v[8][4];
+#pragma unroll
+                for (int u = 0; u < 8; ++u)
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) v[u][k] = (g0 + u < nwg && k < a.n_types) ? w.Q[((size_t)(g0 + u) * 4 + k) * a.H + c] : 0.f;
+#pragma unroll
+                for (int u = 0; u < 8; ++u)
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) t[k] += v[u][k];
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) red[(wave * 4 + k) * 64 + lane] = t[k];
+        __syncthreads();
+        if ((int)threadIdx.x < a.n_types * 64) {
+            const int k = threadIdx.x >> 6, cc = (s - S) * 64 + lane;
+            if (cc < a.H)
+                a.dtype[(size_t)k * a.H + cc] += ((red[k * 64 + lane] + red[(4 + k) * 64 + lane]) + red[(8 + k) * 64 + lane]) + red[(12 + k) * 64 + lane];
+        }
+        return;
+    }
+    const bool pos = blockIdx.y == 1;
+    const int* keys = pos ? w.kp : w.kw;
+    const int key = keys[s];
+    if (key < 0 || (pos ? w.op : w.ow)[key] != s) return;     // not the key's elected (lowest) slot
+    const float* P = pos ? w.Pp : w.Pw;
+    float* dst = pos ? a.dpos : a.dword;
+    float acc[NCH][4];
+#pragma unroll
+    for (int j = 0; j < NCH; ++j)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[j][e] = 0.f;
+    for (int base = s + wave * 64; base < S; base += 256) {  // wave w: slot chunks w, w + 4, .. from the elected slot on, slots in order
+        const int q = base + lane;
+        unsigned long long bits = __ballot(q < S && keys[q] == key);
+        while (bits) {
+            int qs[4], m = 0;
+            for (; m < 4 && bits; ++m) { qs[m] = base + __builtin_ctzll(bits); bits &= bits - 1; }
+            f32x4 v[4][NCH];
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+                if (u < m) {
+#pragma unroll
+                    for (int j = 0; j < NCH; ++j) {
+                        const int c = j * 256 + lane * 4;
+                        if (c < a.H) v[u][j] = *(const f32x4*)(P + (size_t)qs[u] * a.H + c);
+                    }
+                }
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+                if (u < m) {
+#pragma unroll
+                    for (int j = 0; j < NCH; ++j)
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) acc[j][e] += v[u][j][e];
+                }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < NCH; ++j)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) red[wave * 1024 + j * 256 + lane * 4 + e] = acc[j][e];
+    __syncthreads();
+    for (int c = threadIdx.x; c < a.H; c += 256)
+        dst[(size_t)key * a.H + c] += ((red[c] + red[1024 + c]) + red[2048 + c]) + red[3072 + c];
+}
+
+__global__ void fill_i32_kernel(int* p, int v, int n) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) p[i] = v;
 }
 
 // dpos[t][c] = sum_b dz[(b*T + t)*H + c]   (implicit positions: t = row % T); overwrites rows [0, T)
@@ -547,22 +658,57 @@ extern "C" int vk_embed_sum_fwd(const vk_embed_args* a, vk_stream_t s) {
     return check_launch("vk_embed_sum_fwd");
 }
 
+static size_t ws_align(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// Workspace layout (EmbWs), S = 32 * ceil(M / 32) slots: Pw [S, H] | Pp [S, H] (explicit positions) | Q [S / 32, 4, H] | kw [S] | kp [S] | ow [V] | op [P]
+static size_t embed_ws_layout(int M, int H, int V, int P, int has_pos, char* base, EmbWs* w) {
+    const size_t S = (size_t)((M + 31) / 32) * 32;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { char* q = base ? base + off : nullptr; off += ws_align(bytes); return q; };
+    EmbWs x;
+    x.Pw = (float*)take(S * H * 4);
+    x.Pp = has_pos ? (float*)take(S * H * 4) : nullptr;
+    x.Q = (float*)take(S / 32 * 4 * H * 4);
+    x.kw = (int*)take(S * 4);
+    x.kp = has_pos ? (int*)take(S * 4) : nullptr;
+    x.ow = (int*)take((size_t)V * 4);
+    x.op = has_pos ? (int*)take((size_t)P * 4) : nullptr;
+    if (w) *w = x;
+    return off;
+}
+
+extern "C" int64_t vk_embed_bwd_workspace_bytes(int M, int H, int V, int P, int has_pos) {
+    return M <= 0 ? 0 : (int64_t)embed_ws_layout(M, H, V, P, has_pos, nullptr, nullptr);
+}
+
 extern "C" int vk_embed_sum_bwd(const vk_embed_bwd_args* a, vk_stream_t s) {
     if (a->H % 4 || a->H > 1024) return set_error("vk_embed_sum_bwd: H must be a multiple of 4, <= 1024");
     if (a->n_types > 4) return set_error("vk_embed_sum_bwd: at most 4 token types");
     if (a->M <= 0) return 0;
     if (a->T <= 0 || a->M % a->T) return set_error("vk_embed_sum_bwd: M must be a multiple of T (rows are b * T + t)");
-    const int nch = (a->H + 255) / 256;
-    dim3 grid((a->M + 31) / 32), block(256);
+    if (!a->work) return set_error("vk_embed_sum_bwd: no workspace (vk_embed_bwd_workspace_bytes)");
+    const int has_pos = a->pos_ids && a->dpos;
+    EmbWs w;
+    embed_ws_layout(a->M, a->H, a->V, a->P, has_pos, (char*)a->work, &w);
+    const int nch = (a->H + 255) / 256, S = (a->M + 31) / 32 * 32;
     hipStream_t st = (hipStream_t)s;
+    hipLaunchKernelGGL(fill_i32_kernel, dim3((a->V + 255) / 256), dim3(256), 0, st, w.ow, INT_MAX, a->V);
+    if (has_pos) hipLaunchKernelGGL(fill_i32_kernel, dim3((a->P + 255) / 256), dim3(256), 0, st, w.op, INT_MAX, a->P);
+    dim3 grid(S / 32), block(256);
     switch (nch) {
-        case 1: hipLaunchKernelGGL(embed_scatter_kernel<1>, grid, block, 0, st, *a); break;
-        case 2: hipLaunchKernelGGL(embed_scatter_kernel<2>, grid, block, 0, st, *a); break;
-        case 3: hipLaunchKernelGGL(embed_scatter_kernel<3>, grid, block, 0, st, *a); break;
-        default: hipLaunchKernelGGL(embed_scatter_kernel<4>, grid, block, 0, st, *a); break;
+        case 1: hipLaunchKernelGGL(embed_scatter_kernel<1>, grid, block, 0, st, *a, w); break;
+        case 2: hipLaunchKernelGGL(embed_scatter_kernel<2>, grid, block, 0, st, *a, w); break;
+        case 3: hipLaunchKernelGGL(embed_scatter_kernel<3>, grid, block, 0, st, *a, w); break;
+        default: hipLaunchKernelGGL(embed_scatter_kernel<4>, grid, block, 0, st, *a, w); break;
+    }
+    dim3 grid2(S + (a->dtype ? (a->H + 63) / 64 : 0), has_pos ? 2 : 1);
+    switch (nch) {
+        case 1: hipLaunchKernelGGL(embed_combine_kernel<1>, grid2, block, 0, st, *a, w, S); break;
+        case 2: hipLaunchKernelGGL(embed_combine_kernel<2>, grid2, block, 0, st, *a, w, S); break;
+        case 3: hipLaunchKernelGGL(embed_combine_kernel<3>, grid2, block, 0, st, *a, w, S); break;
+        default: hipLaunchKernelGGL(embed_combine_kernel<4>, grid2, block, 0, st, *a, w, S); break;
     }
     if (!a->pos_ids && a->dpos) {
-        if (a->M % a->T) return set_error("vk_embed_sum_bwd: M %% T != 0");
         hipLaunchKernelGGL(embed_pos_reduce_kernel, dim3(a->T, (a->H + 255) / 256), dim3(64), 0, st, (const uint16_t*)a->dz, a->dpos,
                            a->M / a->T, a->T, a->H);
     }

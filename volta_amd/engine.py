@@ -318,6 +318,12 @@ class StepEngine:
         self.bufs[name] = t
         return t
 
+    def embed_ws(self, eb, tag):
+        """Workspace of one embedding backward (vk_embed_sum_bwd: the fixed-order partial sums of its table rows), set into its arguments."""
+        n = L.lib.vk_embed_bwd_workspace_bytes(eb.M, eb.H, eb.V, eb.P, int(bool(eb.pos_ids) and bool(eb.dpos)))
+        eb.work = _addr(self.tmp("embed_ws_" + tag, (max(n, 1),), torch.uint8))
+        return eb
+
     def tmp(self, name, shape, dtype=torch.bfloat16):
         """Backward temporaries are shared by all sub-layers (launches on one stream are ordered).  Ops that are being built for a
         side-stream block run NEXT to main-stream launches: they get temporaries of their own (`_aside`)."""
@@ -660,6 +666,7 @@ class StepEngine:
         self._zero_grad(gtyp)
         eb = self.k(L.EmbedBwdArgs(_addr(dz), None, None, None, _addr(self.G(pre + "word_embeddings.weight")), _addr(gpos), _addr(gtyp),
                                    st.M, st.L, H, cfg.type_vocab_size, cfg.vocab_size, cfg.max_position_embeddings))
+        self.embed_ws(eb, "pre")
         self.patch("input_ids", eb, "ids")
         self.patch("token_type_ids", eb, "type_ids")
         b.append((L.OP_WAIT_SIDE, 12, 0, 0, None, None, None))      # the tied LM decoder's weight gradient (heads, side stream) initialises the table's gradient
@@ -824,6 +831,7 @@ class StepEngine:
         eb = self.k(L.EmbedBwdArgs(_addr(dzt), None, None, None, _addr(self.G(pre + "word_embeddings.weight")), _addr(self.G(pre + "position_embeddings.weight")),
                                    _addr(self.G(pre + "token_type_embeddings.weight")), st_t.M, T, H, cfg.type_vocab_size, cfg.vocab_size,
                                    cfg.max_position_embeddings))
+        self.embed_ws(eb, "vl")
         self.patch("input_ids", eb, "ids")
         self.patch("token_type_ids", eb, "type_ids")
         b.append((L.OP_WAIT_SIDE, 12, 0, 0, None, None, None))      # after the tied LM decoder's weight gradient (heads, side stream)
@@ -919,6 +927,7 @@ class StepEngine:
         # text tokens: word / position / type tables, and the per-sample visual vector
         eb = self.k(L.EmbedBwdArgs(_addr(dzt), None, None, _addr(tpos), _addr(self.G(pre + "word_embeddings.weight")), _addr(self.G(ptab)), _addr(self.G(ttab)),
                                    st_t.M, T, H, cfg.type_vocab_size, cfg.vocab_size, cfg.max_position_embeddings))
+        self.embed_ws(eb, "txt")
         self.patch("input_ids", eb, "ids")
         self.patch("token_type_ids", eb, "type_ids")
         b.append((L.OP_WAIT_SIDE, 12, 0, 0, None, None, None))      # after the tied LM decoder's weight gradient (heads, side stream)
@@ -931,6 +940,7 @@ class StepEngine:
         b.append((L.OP_GENERIC, 0, 0, 0, self.generic(L.FN_MEMSET, p=(dvtab,), n=(dvtab.numel() * 4, 0)), None, None))
         evb = self.k(L.EmbedBwdArgs(_addr(dzv), _addr(word_ids), _addr(twos), _addr(opos), _addr(dvtab), _addr(self.G(ptab)), _addr(self.G(ttab)),
                                     st_v.M, K, H, cfg.type_vocab_size, nword, cfg.max_position_embeddings))
+        self.embed_ws(evb, "vis")
         b.append((L.OP_EMBED_BWD, 0, 0, 0, evb, None, None))
         b.append((L.OP_GENERIC, 0, 0, 0, self.generic(L.FN_COPY, p=(self.G(pre + "object_linguistic_embeddings.weight"), dvtab[0]), n=(H * 4,)), None, None))
         b.append((L.OP_GENERIC, 0, 0, 0, self.generic(L.FN_COPY, p=(self.G(pre + "end_embedding.weight"), dvtab[1]), n=(H * 4,)), None, None))
