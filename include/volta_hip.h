@@ -327,6 +327,19 @@ int vk_rowgroup_sum_bf16(const void* in, void* out, int B, int T, int H, vk_stre
 /* out = dy where y > 0 else 0 (ReLU backward from the kept output), n bf16 elements. */
 int vk_relu_bwd_bf16(const void* dy, const void* y, void* out, int64_t n, vk_stream_t s);
 int vk_copy_async(void* dst, const void* src, int64_t bytes, vk_stream_t s);
+/* Gradient seed of a hidden state that leaves the engine as an fp32 tensor (BertModel.forward, volta_amd/modeling.py): element (b, l, h)
+ * of src, at src + b * stride_b + l * stride_l + h (strides in elements, 0 for expanded gradients, multiples of 4; H a multiple of 8;
+ * src 16-byte aligned), goes to bf16 row row0 + b * L + l, column h of dst (row pitch ld).  accumulate = 0 writes, 1 adds.  src NULL:
+ * the write form zero-fills, the accumulate form launches nothing.  y != NULL (bf16, row pitch ldy, same rows as dst without row0):
+ * the value is kept only where y > 0 -- the gradient at the pre-activation of a ReLU whose output is y (the poolers). */
+typedef struct vk_grad_seed_args {
+    const float* src;
+    int64_t stride_b, stride_l;
+    void* dst;
+    const void* y;
+    int32_t B, L, H, row0, ld, ldy, accumulate, reserved_;
+} vk_grad_seed_args;
+int vk_grad_seed(const vk_grad_seed_args* a, vk_stream_t s);
 
 /* ------------------------------------------------------------------------------------------------
  * Heads and losses, evaluated on labelled rows only.  Replaces BertPreTrainingHeads + the loss code of
@@ -465,6 +478,25 @@ int vk_adamw_step(const vk_adamw_args* a, vk_stream_t s);
 /* The same update (same bits) by `ncus` resident workgroups, each keeping one compute unit to itself and striding over the arena: the form
  * for a step that runs on a stream of its own under the next forward pass, beside GEMM launches that claim the rest of the chip. */
 int vk_adamw_step_on(const vk_adamw_args* a, int ncus, vk_stream_t s);
+/* fp32 tensors OUTSIDE the arena (torch modules trained beside a volta_amd model, volta_amd/optimization.py): one descriptor per tensor,
+ * contiguous, numel elements.  cls selects cls_lr_mult / cls_wd of the vk_adamw_args (VK_CHUNK_SKIP: not touched). */
+typedef struct vk_adamw_tensor {
+    float* p;
+    const float* g;
+    float* m;
+    float* v;
+    int64_t numel;
+    int32_t cls;
+    int32_t reserved_;
+} vk_adamw_tensor;
+/* The update of vk_adamw_step (same element function, same bits for equal inputs) over `n` device descriptors `list` in ONE launch, using
+ * a's class arrays, lr, betas, eps, step_mult, grad_scale and clip; a->p / g / m / v / shadow / chunk_class / n are ignored.
+ * max_numel: the largest numel in the list (sizes the grid). */
+int vk_adamw_step_list(const vk_adamw_args* a, const vk_adamw_tensor* list, int n, int64_t max_numel, vk_stream_t s);
+/* sums[t] = sum of squares of list[t].g (0 for cls == VK_CHUNK_SKIP), t < n, in a fixed order (no atomics, double partials): the slots behind an arena's
+ * chunk sums for vk_grad_norm_from_chunks.  work: n * vk_grad_sqnorm_list_work_floats() floats of scratch. */
+int vk_grad_sqnorm_list(const vk_adamw_tensor* list, int n, int64_t max_numel, float* work, float* sums, vk_stream_t s);
+int vk_grad_sqnorm_list_work_floats(void);
 int vk_axpy_f32(float* y, const float* x, float alpha, int64_t n, vk_stream_t s);
 /* dst[i] = sum_{s < nslabs} src[s * slab_stride + i], i < n (fp32).  Combines the partial weight gradients of a
  * split-K wgrad: each K-chunk is an ordinary problem of the grouped TN launch writing its own slab. */
@@ -561,7 +593,8 @@ enum {
     VK_FN_VLBERT_POSITIONS, /* vk_vlbert_positions(p[0], n[0], n[1], n[2], p[1], p[2]) */
     VK_FN_HOLD,          /* vk_hold_cus(n[0], n[1], n[2]) */
     VK_FN_GATE,          /* vk_gate_wait(p[0], p[1], n[0], p[2]) */
-    VK_FN_BUMP           /* vk_bump_u64(p[0]) */
+    VK_FN_BUMP,          /* vk_bump_u64(p[0]) */
+    VK_FN_GRAD_SEED      /* vk_grad_seed(p[0]) */
 };                       /* VK_FN_POOL_FWD / VK_FN_POOL_BWD: n[3] = fusion mode (VK_FUSE_*) */
 typedef struct vk_generic_args {   /* positional arguments of the small entry points, see executor.cpp */
     int32_t fn;

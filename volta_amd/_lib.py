@@ -126,6 +126,15 @@ class AdamwArgs(C.Structure):
                 ("grad_scale", C.c_float)]
 
 
+class AdamwTensor(C.Structure):
+    _fields_ = [("p", c_p), ("g", c_p), ("m", c_p), ("v", c_p), ("numel", C.c_int64), ("cls", i32), ("reserved_", i32)]
+
+
+class GradSeedArgs(C.Structure):
+    _fields_ = [("src", c_p), ("stride_b", C.c_int64), ("stride_l", C.c_int64), ("dst", c_p), ("y", c_p), ("B", i32), ("L", i32), ("H", i32),
+                ("row0", i32), ("ld", i32), ("ldy", i32), ("accumulate", i32), ("reserved_", i32)]
+
+
 class TailJob(C.Structure):
     _fields_ = [("dst", c_p), ("dst2", c_p), ("src", c_p), ("src2", c_p), ("stride", C.c_int64), ("n", C.c_int64), ("kind", i32), ("count", i32),
                 ("accumulate", i32), ("block_start", i32)]
@@ -147,7 +156,7 @@ class Op(C.Structure):
 (FN_CAST, FN_MEMSET, FN_LOC_FWD, FN_LOC_BWD, FN_ADD_DROPOUT, FN_COLSUM, FN_SELECT, FN_GATHER, FN_SCATTER_ADD,
  FN_LOSS_FINAL, FN_POOL_FWD, FN_POOL_BWD, FN_MASK_PREP, FN_MUL, FN_VLBERT_PREP, FN_VLBERT_MASKGRAD, FN_ROWGROUP_SUM,
  FN_RELU_BWD, FN_COPY, FN_SUM_SLABS, FN_SUM_SLABS_BF16, FN_SIDE_TAIL, FN_QUANT_ROWS, FN_CAST_FP8, FN_VIS_LOSS_FWD, FN_VIS_LOSS_BWD,
- FN_NCE_NEG, FN_TEXT_END_ROWS, FN_VLBERT_OBJ_IDS, FN_VLBERT_POSITIONS, FN_HOLD, FN_GATE, FN_BUMP) = range(1, 34)
+ FN_NCE_NEG, FN_TEXT_END_ROWS, FN_VLBERT_OBJ_IDS, FN_VLBERT_POSITIONS, FN_HOLD, FN_GATE, FN_BUMP, FN_GRAD_SEED) = range(1, 35)
 
 
 class AttnArgs(C.Structure):
@@ -242,6 +251,10 @@ _sig("vk_grad_norm_clip", C.c_int, c_p, C.c_int64, C.c_float, C.c_float, c_p, c_
 _sig("vk_adamw_step", C.c_int, C.POINTER(AdamwArgs), c_p)
 _sig("vk_adamw_step_on", C.c_int, C.POINTER(AdamwArgs), C.c_int, c_p)
 _sig("vk_grad_norm_clip_masked", C.c_int, c_p, C.c_int64, c_p, C.c_float, C.c_float, c_p, c_p, c_p)
+_sig("vk_adamw_step_list", C.c_int, C.POINTER(AdamwArgs), c_p, C.c_int, C.c_int64, c_p)
+_sig("vk_grad_sqnorm_list", C.c_int, c_p, C.c_int, C.c_int64, c_p, c_p, c_p)
+_sig("vk_grad_sqnorm_list_work_floats", C.c_int)
+_sig("vk_grad_seed", C.c_int, C.POINTER(GradSeedArgs), c_p)
 _sig("vk_grad_sqnorm_chunks", C.c_int, c_p, C.c_int64, C.c_int64, c_p, c_p, c_p)
 _sig("vk_grad_norm_from_chunks", C.c_int, c_p, C.c_int64, C.c_float, C.c_float, c_p, c_p)
 _sig("vk_axpy_f32", C.c_int, c_p, c_p, C.c_float, C.c_int64, c_p)
@@ -274,7 +287,7 @@ EXPORTS = ["vk_version", "vk_device_arch", "vk_last_error", "vk_set_seed", "vk_c
            "vk_relu_bwd_bf16", "vk_copy_async", "vk_select_rows", "vk_gather_rows", "vk_scatter_rows_add", "vk_xent_fwd",
            "vk_xent_bwd", "vk_kl_fwd", "vk_kl_bwd", "vk_loss_finalize", "vk_pool_mul_fwd", "vk_pool_mul_bwd",
            "vk_pool_fuse_fwd", "vk_pool_fuse_bwd", "vk_text_end_rows", "vk_vlbert_obj_ids", "vk_vlbert_positions", "vk_vis_loss_fwd", "vk_vis_loss_bwd", "vk_nce_negatives",
-           "vk_mask_prep", "vk_mul_bf16", "vk_grad_norm_workspace_floats", "vk_grad_norm_clip", "vk_grad_norm_clip_masked", "vk_grad_sqnorm_chunks", "vk_grad_norm_from_chunks", "vk_adamw_step", "vk_adamw_step_on",
+           "vk_mask_prep", "vk_mul_bf16", "vk_grad_norm_workspace_floats", "vk_grad_norm_clip", "vk_grad_norm_clip_masked", "vk_grad_sqnorm_chunks", "vk_grad_norm_from_chunks", "vk_adamw_step", "vk_adamw_step_on", "vk_adamw_step_list", "vk_grad_sqnorm_list", "vk_grad_sqnorm_list_work_floats", "vk_grad_seed",
            "vk_axpy_f32", "vk_sum_slabs_f32", "vk_sum_slabs_bf16", "vk_memset_async", "vk_hold_cus", "vk_gate_wait", "vk_bump_u64", "vk_store_u64", "vk_gate_value", "vk_comm_standin", "vk_gemm_reserve_cus", "vk_side_tail", "vk_run_ops", "vk_run_ops_timed", "vk_side_join", "vk_side_join_from", "vk_side_stream", "vk_side_enable", "vk_concap_batch",
            "vk_lmdb_open", "vk_lmdb_close", "vk_lmdb_entries", "vk_lmdb_first", "vk_lmdb_next", "vk_lmdb_get", "vk_concap_record_decode", "vk_concap_records_decode", "vk_b64_decode",
            "vk_wordpiece_open", "vk_wordpiece_close", "vk_wordpiece_vocab_size", "vk_wordpiece_token_id", "vk_wordpiece_encode", "vk_wordpiece_encode_batch"]

@@ -169,6 +169,65 @@ __global__ __launch_bounds__(512) void adamw_narrow_kernel(vk_adamw_args a) {
     }
 }
 
+// Tensors outside the arena (vk_adamw_step_list): blockIdx.y = descriptor, blockIdx.x strides over its elements, four per thread -- one
+// 16-byte access per array where the tensor's four pointers allow it, element by element at a ragged end.  No bf16 copy to refresh.
+__global__ __launch_bounds__(256) void adamw_list_kernel(vk_adamw_args a, const vk_adamw_tensor* list) {
+    const vk_adamw_tensor t = list[blockIdx.y];
+    if (t.cls == VK_CHUNK_SKIP || t.cls < 0 || t.cls > 7) return;
+    const float lr = a.lr * a.cls_lr_mult[t.cls], wd = a.cls_wd[t.cls];
+    const float gs = a.grad_scale * (a.clip ? a.clip[1] : 1.f);
+    const float step = lr * a.step_mult;
+    const bool vec = !(((uintptr_t)t.p | (uintptr_t)t.g | (uintptr_t)t.m | (uintptr_t)t.v) & 15);
+    for (int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4; i < t.numel; i += (int64_t)gridDim.x * 1024) {
+        if (vec && i + 4 <= t.numel) {
+            const f32x4 g = *(const f32x4*)(t.g + i);
+            f32x4 p = *(const f32x4*)(t.p + i), m = *(const f32x4*)(t.m + i), v = *(const f32x4*)(t.v + i);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                float pr = p[r], mr = m[r], vr = v[r];
+                adamw_element(pr, mr, vr, g[r], gs, a.beta1, a.beta2, a.eps, step, lr * wd);
+                p[r] = pr; m[r] = mr; v[r] = vr;
+            }
+            *(f32x4*)(t.p + i) = p; *(f32x4*)(t.m + i) = m; *(f32x4*)(t.v + i) = v;
+        } else {
+            for (int64_t k = i; k < i + 4 && k < t.numel; ++k) {
+                float pr = t.p[k], mr = t.m[k], vr = t.v[k];
+                adamw_element(pr, mr, vr, t.g[k], gs, a.beta1, a.beta2, a.eps, step, lr * wd);
+                t.p[k] = pr; t.m[k] = mr; t.v[k] = vr;
+            }
+        }
+    }
+}
+
+// Per-tensor sums of squares in a fixed order: SQ_LIST_BLOCKS workgroups per tensor write partials (double: a tensor of millions of elements
+// keeps the precision of the arena's per-chunk sums), one wave per tensor adds them.
+constexpr int SQ_LIST_BLOCKS = 64;
+__global__ __launch_bounds__(256) void sqnorm_list_partial_kernel(const vk_adamw_tensor* list, double* work) {
+    __shared__ double sh[4];
+    const vk_adamw_tensor t = list[blockIdx.y];
+    double s = 0.0;
+    if (t.cls != VK_CHUNK_SKIP) {
+        const bool vec = !((uintptr_t)t.g & 15);
+        for (int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4; i < t.numel; i += (int64_t)gridDim.x * 1024) {
+            if (vec && i + 4 <= t.numel) {
+                const f32x4 v = *(const f32x4*)(t.g + i);
+                s += (double)(v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3]);
+            } else {
+                for (int64_t k = i; k < i + 4 && k < t.numel; ++k) s += (double)(t.g[k] * t.g[k]);
+            }
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) work[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+}
+__global__ __launch_bounds__(64) void sqnorm_list_final_kernel(const double* work, float* sums) {
+    double s = work[(size_t)blockIdx.x * SQ_LIST_BLOCKS + threadIdx.x];
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    if (threadIdx.x == 0) sums[blockIdx.x] = (float)s;
+}
+
 __global__ __launch_bounds__(256) void axpy_kernel(float* y, const float* x, float alpha, size_t n4) {
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
         f32x4 a = *(f32x4*)(y + i * 4);
@@ -359,6 +418,30 @@ extern "C" int vk_adamw_step_on(const vk_adamw_args* a, int ncus, vk_stream_t s)
     static const hipError_t attr = hipFuncSetAttribute((const void*)adamw_narrow_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, FOOTPRINT); (void)attr;
     hipLaunchKernelGGL(adamw_narrow_kernel, dim3((unsigned)ncus), dim3(512), FOOTPRINT, (hipStream_t)s, *a);
     return check_launch("vk_adamw_step_on");
+}
+
+static int list_blocks(int64_t max_numel, int cap) {
+    int64_t b = (max_numel + 1023) / 1024;
+    return (int)(b < 1 ? 1 : b > cap ? cap : b);
+}
+
+extern "C" int vk_adamw_step_list(const vk_adamw_args* a, const vk_adamw_tensor* list, int n, int64_t max_numel, vk_stream_t s) {
+    if (n < 0 || n > 65535 || max_numel < 0) return set_error("vk_adamw_step_list: %d tensors, max numel %lld", n, (long long)max_numel);
+    if (n == 0 || max_numel == 0) return 0;
+    hipLaunchKernelGGL(adamw_list_kernel, dim3((unsigned)list_blocks(max_numel, 1024), (unsigned)n), dim3(256), 0, (hipStream_t)s, *a, list);
+    return check_launch("vk_adamw_step_list");
+}
+
+extern "C" int vk_grad_sqnorm_list_work_floats(void) { return 2 * SQ_LIST_BLOCKS; }
+
+extern "C" int vk_grad_sqnorm_list(const vk_adamw_tensor* list, int n, int64_t max_numel, float* work, float* sums, vk_stream_t s) {
+    if (n < 0 || n > 65535 || max_numel < 0) return set_error("vk_grad_sqnorm_list: %d tensors, max numel %lld", n, (long long)max_numel);
+    if (n == 0) return 0;
+    if ((uintptr_t)work & 7) return set_error("vk_grad_sqnorm_list: work needs 8-byte alignment");
+    // the grid does not depend on max_numel: a tensor's sum is the same function of its data whatever else the list holds
+    hipLaunchKernelGGL(sqnorm_list_partial_kernel, dim3(SQ_LIST_BLOCKS, (unsigned)n), dim3(256), 0, (hipStream_t)s, list, (double*)work);
+    hipLaunchKernelGGL(sqnorm_list_final_kernel, dim3((unsigned)n), dim3(64), 0, (hipStream_t)s, (const double*)work, sums);
+    return check_launch("vk_grad_sqnorm_list");
 }
 
 extern "C" int vk_axpy_f32(float* y, const float* x, float alpha, int64_t n, vk_stream_t s) {

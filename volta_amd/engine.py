@@ -36,8 +36,8 @@ def _round_up(x, m):
 class ParamArena:
     """Flat master / shadow / gradient storage; re-points every Parameter at its slice."""
 
-    def __init__(self, model, device):
-        named = list(model.named_parameters())
+    def __init__(self, model, device, prefix=""):
+        named = [(prefix + n, p) for n, p in model.named_parameters()]
         byname = dict(named)
         slots, seen = [], set()
         for name, p in named:
@@ -239,7 +239,8 @@ class StepEngine:
         """fp8: the forward Q|K|V, FFN-up and FFN-down projections of every sub-layer run on the e4m3 MFMA path (csrc/fp8.hip); inputs are
         quantised per row right before the GEMM, weights per output channel whenever they change; the backward stays bf16.
         heads: "pretrain" = the three pre-training heads and losses (BertForVLPreTraining); "tasks" = poolers only, the
-        sequence and pooled outputs leave the engine and their gradients enter it (BertForVLTasks)."""
+        sequence and pooled outputs leave the engine and their gradients enter it (BertForVLTasks); "backbone" = the "tasks" plan without a
+        task, its backward seeded from outside: d(loss)/d(every returned state) enters through `bind_grads` (BertModel on its own)."""
         self.cfg, self.arena, self.B, self.T, self.Rv, self.train = cfg, arena, B, T, Rv, train
         self.heads = heads
         self.task = task              # heads == "tasks": (task id, its task_cfg entry) -- the classifier built behind the poolers
@@ -309,6 +310,7 @@ class StepEngine:
         self.seed = torch.zeros(1, dtype=torch.int64, device=dev)
         self.inputs = {}              # name -> list of (struct, field) patched every step
         self.taps = {}
+        self.grad_seeds = {}          # heads == "backbone": output name -> vk_grad_seed_args whose source bind_grads() patches every backward
         self._build()
 
     # ---------------------------------------------------------------- helpers
@@ -595,6 +597,8 @@ class StepEngine:
         self.n_sub = len(list(sublayer_schedule(cfg)))
         self.fwd_sub_start = []       # forward op index at which sub-layer k begins (the optimizer overlap cuts the list there)
         self.sublayer_ids = [n for n, _ in sched]       # taps "t<n>" / "v<n>": both streams' states after sub-layer n, forward order
+        backbone = self.heads == "backbone"
+        v_level0 = []                 # backbone, vision embedding aside: seeds of vision states no sub-layer has transformed yet
         for k, (n, typ) in enumerate(sched):
             self.sub_k = k
             self.fwd_sub_start.append(len(self.fwd.ops))
@@ -603,8 +607,19 @@ class StepEngine:
             ops = self._attn_sublayer(n) if typ == "attn" else self._ffn_sublayer(n)
             if k + 2 < self.n_sub:
                 ops.insert(0, (L.OP_WAIT_SIDE, (k + 2) % 8, 0, 0, None, None, None))
+            if backbone and k + 1 < self.n_sub:
+                # d(loss)/d(state after sub-layer n), output_all_encoded_layers: added into the stream's current dX buffer at the head of the
+                # sub-layer's backward stage, before anything reads it (the final states are the seeds of the heads' backward).  A stream the
+                # sub-layer does not transform keeps its buffer, so the add lands where the next reader looks either way -- except for a
+                # vision embedding that runs aside: its backward reads dX[1] from the side stream behind sub-layer k_vis, so the seeds of
+                # the untransformed vision states go in front of that fork instead
+                head = []
+                for m, tag in ((0, "t"), (1, "v")):
+                    op = self._seed_op("%s%d" % (tag, n), self._dx(m, self.level[m] % 2), self.B, self.st[m].L, self.st[m].H, accumulate=1)
+                    (v_level0 if (m == 1 and emb_image_aside and self.level[1] == 0) else head).append(op)
+                ops[0:0] = head
             if emb_image_aside and k == k_vis:
-                ops = ops + emb_image_bwd                                   # d(loss)/d(vision embedding) is final after this sub-layer's backward
+                ops = ops + v_level0 + emb_image_bwd                        # d(loss)/d(vision embedding) is final after this sub-layer's backward
             bwd_stages.append(ops)
             self.taps["t%d" % n], self.taps["v%d" % n] = self.x[0], self.x[1]
         self.fwd_heads_start = len(self.fwd.ops)
@@ -637,6 +652,32 @@ class StepEngine:
         self.level[m] += 1
         k = self.level[m]
         return self._dx(m, k % 2), self._dx(m, (k - 1) % 2)
+
+    def _seed_op(self, name, dst, B, L_, H, y=None, accumulate=0):
+        """A vk_grad_seed launch into the bf16 gradient buffer dst [B * L_, H] from the fp32 gradient of output `name` (patched by bind_grads)."""
+        a = self.k(L.GradSeedArgs(None, 0, 0, _addr(dst), _addr(y), B, L_, H, 0, dst.stride(0), y.stride(0) if y is not None else 0, accumulate, 0))
+        assert name not in self.grad_seeds, name
+        self.grad_seeds[name] = a
+        return (L.OP_GENERIC, 0, 0, 0, self.generic(L.FN_GRAD_SEED, p=(a,)), None, None)
+
+    def bind_grads(self, grads):
+        """heads == "backbone": point the seed launches at this backward's gradients {output name: fp32 tensor or None}.  A gradient whose
+        layout the kernel cannot read (stride along H other than 1, unaligned) is copied contiguous once; None zero-fills a final state /
+        pooled seed and skips an intermediate one.  Returns the tensors the launches read (keep them alive until the backward is issued)."""
+        keep = []
+        for name, a in self.grad_seeds.items():
+            g = grads.get(name)
+            if g is None:
+                a.src, a.stride_b, a.stride_l = None, 0, 0
+                continue
+            g3 = g if g.dim() == 3 else g.unsqueeze(1)
+            if not (g3.dtype == torch.float32 and g3.device == self.dev and g3.stride(2) == 1 and g3.stride(0) % 4 == 0 and g3.stride(1) % 4 == 0
+                    and g3.data_ptr() % 16 == 0):
+                g3 = g3.to(device=self.dev, dtype=torch.float32).contiguous()
+            assert tuple(g3.shape) == (a.B, a.L, a.H), (name, tuple(g.shape), (a.B, a.L, a.H))
+            keep.append(g3)
+            a.src, a.stride_b, a.stride_l = g3.data_ptr(), g3.stride(0), g3.stride(1)
+        return keep
 
     def _zero_grad(self, t):
         self.bwd_pro.append((L.OP_GENERIC, 0, 0, 0, self.generic(L.FN_MEMSET, p=(t,), n=(t.numel() * t.element_size(), 0)), None, None))
@@ -1615,12 +1656,23 @@ class StepEngine:
                 self._zero_grad(self.G(nm))
         b = []
         dxh = [self._dx(m, self.level[m] % 2) for m in range(2)]
-        for m in range(2):                                 # the sequence outputs feed nothing but the task head
-            b.append((L.OP_GENERIC, 0, 0, 0, self.generic(L.FN_MEMSET, p=(dxh[m],), n=(dxh[m].numel() * 2, 0)), None, None))
+        backbone = self.heads == "backbone"
+        for m in range(2):
+            if backbone:                                   # d(loss)/d(seq_t), d(loss)/d(seq_v) from outside, written before the poolers add theirs
+                b.append(self._seed_op(("seq_t", "seq_v")[m], dxh[m], B, self.st[m].L, self.st[m].H))
+            else:                                          # the sequence outputs feed nothing but the task head
+                b.append((L.OP_GENERIC, 0, 0, 0, self.generic(L.FN_MEMSET, p=(dxh[m],), n=(dxh[m].numel() * 2, 0)), None, None))
         self.pred = self.d_pred = None
         heads_of_other_tasks = [nm for nm in self.arena.params if nm.startswith("clfs_dict.")]
         dpool = [None, None]                               # gradients at the poolers' pre-activation outputs
-        if self.task is not None:
+        if backbone:
+            if self.task is not None:
+                raise ValueError("the backbone plan has no task head")
+            for m, (py, nm) in enumerate(((pt, "pooled_t"), (pv, "pooled_v"))):
+                if py is not None:                         # ReLU poolers: d pre-activation = d pooled * (pooled > 0)
+                    dpool[m] = self.buf("d_" + nm, (B, P))
+                    b.append(self._seed_op(nm, dpool[m], B, 1, P, y=py))
+        elif self.task is not None:
             task_id, tcfg = self.task
             typ = tcfg["type"]
             pre = "clfs_dict.%s." % task_id

@@ -48,6 +48,7 @@ class PreTrainedModel(nn.Module):
 
     config_class = BertConfig
     base_model_prefix = "bert"
+    _arena_prefix = ""
 
     def __init__(self, config, *inputs, **kwargs):
         super().__init__()
@@ -172,8 +173,33 @@ class BertEncoder(M.Holder):
         self.layer = nn.ModuleList(layers)
 
 
+class _BackboneStep(torch.autograd.Function):
+    """A standalone BertModel's forward as one autograd node.  Outputs (fp32): the final text / vision states, the pooled vectors the fusion
+    method has, then with output_all_encoded_layers the states after every sub-layer but the last.  Their gradients re-enter the engine as
+    the seeds of its backward list; a gradient autograd does not materialise (None) costs no pass."""
+
+    @staticmethod
+    def forward(ctx, model, anchor, tensors, all_layers):
+        ctx.set_materialize_grads(False)
+        outs = model._backbone_forward(tensors, all_layers)
+        ctx.model, ctx.serial, ctx.names = model, model._fwd_serial, [n for n, _ in outs]
+        return tuple(t for _, t in outs)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        ctx.model._backbone_backward(ctx, dict(zip(ctx.names, grads)))
+        return None, None, None, None
+
+
 class BertModel(PreTrainedModel):
-    """Embeddings + gated encoder + poolers (volta/encoders.py:918-1017)."""
+    """Embeddings + gated encoder + poolers (volta/encoders.py:918-1017).
+
+    Inside BertForVLPreTraining / BertForVLTasks it is the parameter container of the root model, and `forward` is the root's `encode()`
+    (no gradient).  Constructed on its own it is a root model: it owns its arena and engines, and `forward` runs the engine's forward and,
+    under autograd, its backward, seeded by the gradients of whatever torch code consumes the outputs (a custom task head)."""
+
+    _heads_mode = "backbone"
+    _arena_prefix = "bert."        # the engine addresses parameters by the names they have inside the root models
 
     def __init__(self, config):
         super().__init__(config)
@@ -204,14 +230,89 @@ class BertModel(PreTrainedModel):
             self.v_pooler.add_module("dense", M.LinearParams(config.v_hidden_size, config.v_pooler_size))
         M.init_bert_(self, config.initializer_range)
         M.special_init_embeddings_(self.embeddings, kind, config)
+        # root-model state; a root model that builds this BertModel takes its parameters and removes the flag (_adopt)
+        self.add_global_imgfeat = int(config.add_global_imgfeat is not None)
+        self.__dict__.update(_vk_is_model=True, _arena=None, _engines={}, _step=0, _seed_base=None, _last=None, _ddp=None, _fwd_serial=0)
+        for p in self.parameters():
+            p._vk_owner = self
 
     def forward(self, input_txt, input_imgs, image_loc, token_type_ids=None, attention_mask=None,
                 image_attention_mask=None, output_all_encoded_layers=False, output_all_attention_masks=False):
+        """The reference's signature and result (encoders.py:954-1017): (seq_t [B,T,H], seq_v [B,Rv,Hv], pooled_t, pooled_v, attention maps);
+        with `output_all_encoded_layers` the two sequences are lists of both streams' states after every sub-layer.  Standalone, the
+        outputs are fp32 and differentiable with respect to every parameter; the attention maps are returned DETACHED (no gradient flows
+        through them).  Nested in a root model this is the root's `encode()`, without gradient."""
         root = self.__dict__.get("_root")
-        if root is None:
-            raise NotImplementedError("BertModel runs as part of BertForVLPreTraining (the HIP plan includes the heads)")
-        return root.encode(input_txt, input_imgs, image_loc, token_type_ids, attention_mask, image_attention_mask,
-                           output_all_encoded_layers=output_all_encoded_layers, output_all_attention_masks=output_all_attention_masks)
+        if root is not None:
+            return root.encode(input_txt, input_imgs, image_loc, token_type_ids, attention_mask, image_attention_mask,
+                               output_all_encoded_layers=output_all_encoded_layers, output_all_attention_masks=output_all_attention_masks)
+        tensors, B, T, Rv = self._prep_inputs(input_txt, input_imgs, image_loc, token_type_ids, attention_mask, image_attention_mask,
+                                              None, None, None, None)
+        all_layers = bool(output_all_encoded_layers)
+        self.__dict__["_want_attn_maps"] = bool(output_all_attention_masks and self.config.visualization)
+        try:
+            self.materialize()
+            from .optimization import flush_clip
+            flush_clip(self._arena)      # a pending clip coefficient belongs to the gradients as they are now, before autograd adds to any of them
+            if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+                anchor = next(p for p in self.parameters() if p.requires_grad)
+                flat = _BackboneStep.apply(self, anchor, tensors, all_layers)
+                names = [n for n, _ in self._backbone_outputs(self._last[0], all_layers)]
+            else:
+                with torch.no_grad():
+                    outs = self._backbone_forward(tensors, all_layers)
+                names, flat = [n for n, _ in outs], [t for _, t in outs]
+        finally:
+            self.__dict__["_want_attn_maps"] = False
+        out = dict(zip(names, flat))
+        eng = self._last[0]
+        attn_maps = _attention_maps(self.config, eng, output_all_attention_masks)
+        if all_layers:
+            last = eng.sublayer_ids[-1]
+            seq_t = [out["t%d" % n] for n in eng.sublayer_ids if n != last] + [out["seq_t"]]
+            seq_v = [out["v%d" % n] for n in eng.sublayer_ids if n != last] + [out["seq_v"]]
+        else:
+            seq_t, seq_v = out["seq_t"], out["seq_v"]
+        return seq_t, seq_v, out.get("pooled_t"), out.get("pooled_v"), attn_maps
+
+    # ------------------------------------------------------------------ standalone root model
+    def _adopt(self, root):
+        """Called by the root model that holds this BertModel: the parameters become the root's, the standalone state goes."""
+        self.__dict__["_root"] = root
+        for k in ("_vk_is_model", "_arena", "_engines", "_step", "_seed_base", "_last", "_ddp", "_fwd_serial"):
+            self.__dict__.pop(k, None)
+
+    def _backbone_outputs(self, eng, all_layers):
+        """[(output name, bf16 engine buffer)] in the order of _BackboneStep's outputs."""
+        B, T, Rv = eng.B, eng.T, eng.Rv
+        H, Hv = self.config.hidden_size, self.config.v_hidden_size
+        outs = [("seq_t", eng.taps["seq_t"].view(B, T, H)), ("seq_v", eng.taps["seq_v"].view(B, Rv, Hv))]
+        outs += [(n, eng.taps[n]) for n in ("pooled_t", "pooled_v") if eng.taps[n] is not None]
+        if all_layers:
+            ids = eng.sublayer_ids[:-1]
+            outs += [("t%d" % n, eng.taps["t%d" % n].view(B, T, H)) for n in ids] + [("v%d" % n, eng.taps["v%d" % n].view(B, Rv, Hv)) for n in ids]
+        return outs
+
+    def _backbone_forward(self, tensors, all_layers):
+        self._engine_forward(tensors)
+        self.__dict__["_fwd_serial"] += 1
+        return [(n, t.float()) for n, t in self._backbone_outputs(self._last[0], all_layers)]
+
+    def _backbone_backward(self, ctx, grads):
+        if getattr(ctx, "done", False):
+            raise RuntimeError("volta_amd.BertModel: a second backward through the same forward (its engine state was consumed by the first)")
+        if ctx.serial != self._fwd_serial:
+            raise RuntimeError("volta_amd.BertModel: this backward belongs to a forward that a later forward of the same model has overtaken; "
+                               "its activations are gone (run backward before the next forward)")
+        ctx.done = True
+        eng, _ = self._last
+        # a pooler whose output received no gradient gets none, as under autograd (the engine's pass writes zeros into its arena slots)
+        absent = {"bert.%s.dense.%s" % (p, w) for o, p in (("pooled_t", "t_pooler"), ("pooled_v", "v_pooler")) if o in grads and grads[o] is None
+                  for w in ("weight", "bias")}
+        state = self._backward_begin(eng, absent=absent)
+        keep = eng.bind_grads(grads)
+        self._backward_run(eng, state)
+        del keep
 
 
 class BertPreTrainingHeads(M.Holder):
@@ -278,7 +379,7 @@ class BertForVLPreTraining(PreTrainedModel):
         self.__dict__["_seed_base"] = None
         self.__dict__["_last"] = None
         self.__dict__["_ddp"] = None
-        self.bert.__dict__["_root"] = self
+        self.bert._adopt(self)
         for mod in self.modules():
             if mod is not self and isinstance(mod, PreTrainedModel):
                 mod.__dict__["_root"] = self
@@ -304,7 +405,7 @@ class BertForVLPreTraining(PreTrainedModel):
                                "there is no CPU execution path")
         arena = self.__dict__.get("_arena")
         if arena is None or arena.device != dev or not arena.intact():
-            self.__dict__["_arena"] = ParamArena(self, dev)
+            self.__dict__["_arena"] = ParamArena(self, dev, prefix=self._arena_prefix)
             self.__dict__["_engines"] = {}
             for p in self.parameters():
                 p._vk_owner = self
@@ -403,9 +504,10 @@ class BertForVLPreTraining(PreTrainedModel):
         torch.cat([g_lm.reshape(1), g_img.reshape(1), g_nsp.reshape(1)], out=eng.gout)      # one launch, no temporary
         self._backward_run(eng, state)
 
-    def _backward_begin(self, eng):
-        """Gradient-accumulation bookkeeping shared by the pre-training and the task models.  Parameters of torch-side head
-        modules (`_torch_param_prefixes`) get their gradients from autograd (redirected into the arena by a hook)."""
+    def _backward_begin(self, eng, absent=()):
+        """Gradient-accumulation bookkeeping shared by the root models.  Parameters of torch-side head modules (`_torch_param_prefixes`) get
+        their gradients from autograd (redirected into the arena by a hook).  `absent`: arena names that receive no gradient in this
+        backward (a standalone BertModel's pooler whose output got none) -- left as they are, like `unused_params`."""
         arena = eng.arena
         from .optimization import flush_clip
         flush_clip(arena)                   # a clip coefficient no optimizer step has consumed applies to the gradients it was computed for
@@ -414,7 +516,7 @@ class BertForVLPreTraining(PreTrainedModel):
         # optimizer and clip_grad_norm_ then leave their arena chunks alone
         unused = eng.unused_params          # e.g. the VQA text pooler in pre-training: no launch reads it, .grad stays None
         pairs = [((n, p), g) for (n, p), g in zip(arena.param_list(), arena.grad_views())
-                 if p.requires_grad and not (skip and n.startswith(skip)) and n not in unused]
+                 if p.requires_grad and not (skip and n.startswith(skip)) and n not in unused and n not in absent]
         params, gviews = [x[0] for x in pairs], [x[1] for x in pairs]
         n_have = sum(p.grad is not None for _, p in params)
         accumulate = n_have == len(params)
@@ -562,6 +664,20 @@ class BertForVLPreTraining(PreTrainedModel):
         return seq_t, seq_v, None if pt is None else pt.float(), None if pv is None else pv.float(), attn_maps
 
 
+# a standalone BertModel is a root model with the same engine plumbing (nested in a root model, `_root` routes everything to the root)
+for _name in ("set_dropout_seed", "_engine", "_prep_inputs", "_engine_forward", "_backward_begin", "_backward_run", "set_projection_dtype"):
+    setattr(BertModel, _name, getattr(BertForVLPreTraining, _name))
+
+
+def _bert_materialize(self, device=None):
+    root = self.__dict__.get("_root")
+    return root.materialize(device) if root is not None else BertForVLPreTraining.materialize(self, device)
+
+
+_bert_materialize.__doc__ = BertForVLPreTraining.materialize.__doc__
+BertModel.materialize = _bert_materialize
+
+
 def _attention_maps(config, eng, requested):
     """all_attention_mask of BertEncoder.forward (volta/encoders.py:858-886): empty lists unless requested; one entry per attention
     sub-layer otherwise -- the dictionaries of encoders.py:342-356 under config.visualization, None without it (:357-358)."""
@@ -670,7 +786,7 @@ class BertForVLTasks(PreTrainedModel):
         self.__dict__["_seed_base"] = None
         self.__dict__["_last"] = None
         self.__dict__["_ddp"] = None
-        self.bert.__dict__["_root"] = self
+        self.bert._adopt(self)
         for mod in self.modules():
             if mod is not self and isinstance(mod, PreTrainedModel):
                 mod.__dict__["_root"] = self

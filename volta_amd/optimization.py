@@ -21,14 +21,43 @@ from torch.optim.lr_scheduler import LambdaLR
 from . import _lib as L
 
 
-def _arena_of(params):
-    owners = {id(getattr(p, "_vk_owner", None)): getattr(p, "_vk_owner", None) for p in params}
-    if len(owners) != 1 or None in owners.values():
-        raise RuntimeError("volta_amd optimizers need parameters owned by one volta_amd model on the GPU: call "
-                           "model.cuda() and model.materialize() (or run one forward) before building the optimizer")
-    model = next(iter(owners.values()))
-    arena = model.materialize()
-    return model, arena
+def _split_params(params, labels=None):
+    """(model, arena, foreign) of a parameter set that may mix ONE volta_amd model's arena parameters with plain CUDA fp32 tensors on the
+    same device (a torch head trained on top of a standalone BertModel).  model / arena are None without arena parameters.  Anything else
+    raises, naming the offending parameter by `labels[i]` (default: its position)."""
+    labels = labels or ["parameter %d" % i for i in range(len(params))]
+    owners, foreign = {}, []
+    for p, lab in zip(params, labels):
+        o = getattr(p, "_vk_owner", None)
+        if o is not None:
+            owners.setdefault(id(o), (o, lab))
+        else:
+            foreign.append((p, lab))
+    if len(owners) > 1:
+        (_, a), (_, b) = list(owners.values())[:2]
+        raise RuntimeError("volta_amd optimizers take the parameters of at most one volta_amd model: %s and %s belong to different models" % (a, b))
+    model = arena = None
+    if owners:
+        model = next(iter(owners.values()))[0]
+        arena = model.materialize()
+    dev = arena.device if arena is not None else None
+    for p, lab in foreign:
+        if not isinstance(p, torch.Tensor) or p.device.type != "cuda" or p.dtype != torch.float32 or not p.is_contiguous():
+            raise RuntimeError("volta_amd optimizers: %s is not a contiguous CUDA float32 tensor nor a volta_amd model's parameter (%s)"
+                               % (lab, (p.dtype, tuple(p.shape), str(p.device)) if isinstance(p, torch.Tensor) else type(p).__name__))
+        dev = dev or p.device
+        if p.device != dev:
+            raise RuntimeError("volta_amd optimizers: %s is on %s, the other parameters on %s" % (lab, p.device, dev))
+    return model, arena, [p for p, _ in foreign]
+
+
+def _tensor_list(entries, device):
+    """Device array of vk_adamw_tensor descriptors for [(p, g, m, v, class)] and the largest numel (the grid of the list launches)."""
+    rows = [(p.data_ptr(), g.data_ptr(), m.data_ptr() if m is not None else 0, v.data_ptr() if v is not None else 0, p.numel(), c)
+            for p, g, m, v, c in entries]
+    host = (L.AdamwTensor * len(rows))(*[L.AdamwTensor(a, b, c_ or None, d or None, n, k, 0) for a, b, c_, d, n, k in rows])
+    dev = torch.frombuffer(bytearray(host), dtype=torch.uint8).to(device, non_blocking=False)
+    return dev, max((r[4] for r in rows), default=0)
 
 
 def _chunks_of(arena, name):
@@ -75,20 +104,25 @@ class AdamW(Optimizer):
         # start a backward whose sharded gradients no volta_amd optimizer would pick up, and the reference's order is model -> DDP -> optimizer
         # -> first backward (train_concap.py:227-253).  Parameters that are not (yet) a materialised volta_amd model's stay lazy (_setup).
         try:
-            _, arena = _arena_of([p for g in self.param_groups for p in g["params"]])
-            arena._vk_adamw = weakref.ref(self)
+            _, arena, _ = _split_params([p for g in self.param_groups for p in g["params"]])
+            if arena is not None:
+                arena._vk_adamw = weakref.ref(self)
         except RuntimeError:
             pass
 
     def _setup(self):
         allp = [p for g in self.param_groups for p in g["params"]]
-        model, arena = _arena_of(allp)
-        byptr = {p.data_ptr(): n for n, p in arena.params.items()}
+        labels = ["param_groups[%d]['params'][%d]" % (gi, i) for gi, g in enumerate(self.param_groups) for i in range(len(g["params"]))]
+        model, arena, foreign = _split_params(allp, labels)
+        if arena is None and not foreign:
+            raise RuntimeError("volta_amd.AdamW: no parameters")
+        byptr = {p.data_ptr(): n for n, p in arena.params.items()} if arena is not None else {}
+        fids = {id(p) for p in foreign}
         # classes: groups with identical (initial lr, wd, betas, eps, correct_bias) share one class; chunks of parameters the
         # optimizer was not given (frozen: train_concap.py:200,213 builds its groups from requires_grad parameters) are skipped
-        classes, cls_of_chunk = [], torch.full((arena.total // 1024,), L.CHUNK_SKIP, dtype=torch.uint8)
+        classes, cls_of_chunk = [], torch.full(((arena.total if arena is not None else 0) // 1024,), L.CHUNK_SKIP, dtype=torch.uint8)
         hyper = None
-        spans = []
+        spans, fspans = [], []
         for g in self.param_groups:
             h = (tuple(g["betas"]), g["eps"], g["correct_bias"])
             hyper = hyper or h
@@ -101,14 +135,20 @@ class AdamW(Optimizer):
                 classes.append((key, g))
             ci = [c[0] for c in classes].index(key)
             for p in g["params"]:
+                if id(p) in fids:              # outside the arena: moments of its own, stepped by vk_adamw_step_list
+                    fspans.append(dict(p=p, cls=ci, m=torch.zeros_like(p), v=torch.zeros_like(p)))
+                    continue
                 n = byptr[p.data_ptr()]
                 c0, c1 = _chunks_of(arena, n)
                 cls_of_chunk[c0:c1] = ci
                 spans.append((p, n, c0, c1))
+        if arena is None:
+            self._fused = dict(model=None, arena=None, classes=classes, spans=[], foreign=fspans, step=0)
+            return
         _check_shared_chunks(arena, {n for _, n, _, _ in spans}, "given to the optimizer")
         arena._vk_adamw = weakref.ref(self)       # clip_grad_norm_ hands its coefficient to this optimizer's next step (see there)
         self._fused = dict(model=model, arena=arena, classes=classes, base_class=cls_of_chunk, spans=spans, masks={},
-                           chunk_class=cls_of_chunk.to(arena.device),
+                           chunk_class=cls_of_chunk.to(arena.device), foreign=fspans,
                            m=torch.zeros_like(arena.master), v=torch.zeros_like(arena.master), step=0)
 
     def _chunk_class_for_step(self):
@@ -145,10 +185,14 @@ class AdamW(Optimizer):
             self._setup()
         f = self._fused
         arena = f["arena"]
+        if f.get("foreign", ()) and self._zero1_reducer() is not None:
+            raise NotImplementedError("volta_amd.AdamW: data-parallel mode 'zero1' with parameters outside the model's arena")
         f["step"] += 1
-        g0 = self.param_groups[0]
-        b1, b2 = g0["betas"]
         a = L.AdamwArgs()
+        if arena is None:                  # torch tensors only
+            self._fill_hyper(a, f)
+            self._step_foreign(a)
+            return loss
         a.p, a.g, a.m, a.v = arena.master.data_ptr(), arena.grad.data_ptr(), f["m"].data_ptr(), f["v"].data_ptr()
         a.shadow, a.chunk_class = arena.shadow.data_ptr(), self._chunk_class_for_step().data_ptr()
         pend = getattr(arena, "pending_clip", None)
@@ -161,13 +205,7 @@ class AdamW(Optimizer):
         a.clip = clip.data_ptr() if clip is not None else None
         arena.pending_clip = None
         a.n = arena.total
-        for i, (key, grp) in enumerate(f["classes"]):
-            a.cls_lr_mult[i] = grp["lr"]          # current (scheduled) lr of the class
-            a.cls_wd[i] = grp["weight_decay"]
-        a.lr, a.beta1, a.beta2, a.eps = 1.0, b1, b2, g0["eps"]
-        t = f["step"]
-        a.step_mult = math.sqrt(1.0 - b2 ** t) / (1.0 - b1 ** t) if g0["correct_bias"] else 1.0
-        a.grad_scale = grad_scale
+        self._fill_hyper(a, f, grad_scale)
         arena.sync_optimizer()         # an earlier pipelined step nobody waited for (two steps without a forward in between)
         red = self._zero1_reducer()
         if red is not None:
@@ -177,11 +215,42 @@ class AdamW(Optimizer):
         else:
             self._step_pipelined(a, arena, clip)
         arena.mark_shadow_fresh()      # the kernel refreshed the bf16 copies itself
+        self._step_foreign(a)          # same arguments (classes, step, scale, deferred clip), on the current stream
         return loss
 
+    def _fill_hyper(self, a, f, grad_scale=1.0):
+        """Class lr / wd, betas, eps, bias correction and gradient scale of this step into vk_adamw_args `a`."""
+        g0 = self.param_groups[0]
+        b1, b2 = g0["betas"]
+        for i, (key, grp) in enumerate(f["classes"]):
+            a.cls_lr_mult[i] = grp["lr"]          # current (scheduled) lr of the class
+            a.cls_wd[i] = grp["weight_decay"]
+        a.lr, a.beta1, a.beta2, a.eps = 1.0, b1, b2, g0["eps"]
+        t = f["step"]
+        a.step_mult = math.sqrt(1.0 - b2 ** t) / (1.0 - b1 ** t) if g0["correct_bias"] else 1.0
+        a.grad_scale = grad_scale
+
+    def _step_foreign(self, a):
+        """One vk_adamw_step_list launch over the tensors outside the arena that carry a gradient (the others are skipped, as
+        pytorch_transformers' AdamW skips `p.grad is None`)."""
+        f = self._fused
+        live = [(t["p"], t["p"].grad, t["m"], t["v"], t["cls"]) for t in f.get("foreign", ()) if t["p"].grad is not None]
+        if not live:
+            return
+        for p, g, _, _, _ in live:
+            if g.dtype != torch.float32 or not g.is_contiguous() or g.shape != p.shape or g.device != p.device:
+                raise RuntimeError("volta_amd.AdamW: the gradient of a tensor outside the arena must be a contiguous float32 tensor of its shape")
+        key = tuple((p.data_ptr(), g.data_ptr()) for p, g, _, _, _ in live)
+        if f.get("flist_key") != key:          # .grad tensors change when autograd allocates new ones (zero_grad(set_to_none=True))
+            f["flist"], f["flist_max"] = _tensor_list(live, live[0][0].device)
+            f["flist_key"] = key
+        L.check(L.lib.vk_adamw_step_list(C.byref(a), L.ptr(f["flist"]), len(live), f["flist_max"], L.stream_ptr()))
+
     def _grad_names(self):
-        """Names of this optimizer's parameters that carry a gradient now (the set a deferred clip coefficient must have been computed over)."""
-        return frozenset(n for p, n, _, _ in self._fused["spans"] if p.grad is not None)
+        """Names of this optimizer's parameters that carry a gradient now (the set a deferred clip coefficient must have been computed over);
+        tensors outside the arena count as ("foreign", id)."""
+        f = self._fused
+        return frozenset([n for p, n, _, _ in f["spans"] if p.grad is not None] + [("foreign", id(t["p"])) for t in f.get("foreign", ()) if t["p"].grad is not None])
 
     def _zero1_reducer(self):
         """The data-parallel wrapper's reducer when it runs in mode "zero1" and the last backward left this rank with shards to step."""
@@ -256,17 +325,22 @@ class AdamW(Optimizer):
 
     def synchronize(self):
         """Current stream waits for a pipelined step (needed only before host code reads parameters without a device sync)."""
-        if self._fused is not None:
+        if self._fused is not None and self._fused["arena"] is not None:
             self._fused["arena"].sync_optimizer()
 
     # ---- checkpoint interchange (volta/train_utils.py:295-340 saves optimizer.state_dict() of pytorch_transformers'
     # AdamW: per parameter {"step", "exp_avg", "exp_avg_sq"}, indexed in param_groups order)
     def _spans(self):
+        """Per parameter in param_groups order: (arena offset, numel, shape) or, outside the arena, its foreign entry."""
         arena = self._fused["arena"]
-        byptr = {p.data_ptr(): n for n, p in arena.params.items()}
+        byptr = {p.data_ptr(): n for n, p in arena.params.items()} if arena is not None else {}
+        fmap = {id(t["p"]): t for t in self._fused.get("foreign", ())}
         out = []
         for g in self.param_groups:
             for p in g["params"]:
+                if id(p) in fmap:
+                    out.append(fmap[id(p)])
+                    continue
                 n = byptr[p.data_ptr()]
                 numel = 1
                 for d in arena.shape[n]:
@@ -298,8 +372,10 @@ class AdamW(Optimizer):
         sd = super().state_dict()
         if self._fused is not None and self._fused["step"] > 0:
             f = self._fused
-            sd["state"] = {i: {"step": f["step"], "exp_avg": f["m"][o:o + n].view(shape).clone(), "exp_avg_sq": f["v"][o:o + n].view(shape).clone()}
-                           for i, (o, n, shape) in enumerate(self._spans())}
+            sd["state"] = {i: ({"step": f["step"], "exp_avg": sp["m"].clone(), "exp_avg_sq": sp["v"].clone()} if isinstance(sp, dict) else
+                               {"step": f["step"], "exp_avg": f["m"][sp[0]:sp[0] + sp[1]].view(sp[2]).clone(),
+                                "exp_avg_sq": f["v"][sp[0]:sp[0] + sp[1]].view(sp[2]).clone()})
+                           for i, sp in enumerate(self._spans())}
         return sd
 
     def load_state_dict(self, state_dict):
@@ -315,17 +391,22 @@ class AdamW(Optimizer):
         if len(state) != len(spans):
             raise ValueError("volta_amd.AdamW.load_state_dict: the checkpoint holds %d parameter states, the optimizer %d parameters" % (len(state), len(spans)))
         steps = set()
-        for i, (o, n, shape) in enumerate(spans):
+        for i, sp in enumerate(spans):
             st = state[i] if i in state else state[str(i)]
-            f["m"][o:o + n].copy_(st["exp_avg"].reshape(-1))
-            f["v"][o:o + n].copy_(st["exp_avg_sq"].reshape(-1))
+            if isinstance(sp, dict):
+                sp["m"].copy_(st["exp_avg"].reshape(sp["m"].shape))
+                sp["v"].copy_(st["exp_avg_sq"].reshape(sp["v"].shape))
+            else:
+                o, n, shape = sp
+                f["m"][o:o + n].copy_(st["exp_avg"].reshape(-1))
+                f["v"][o:o + n].copy_(st["exp_avg_sq"].reshape(-1))
             steps.add(int(st["step"]))
         if len(steps) != 1:
             raise ValueError("volta_amd.AdamW.load_state_dict: parameters at different step counts %s (one fused launch updates all of them)" % sorted(steps))
         f["step"] = steps.pop()
 
     def zero_grad(self, set_to_none=True):
-        if self._fused is not None:
+        if self._fused is not None and self._fused["arena"] is not None:
             self._fused["arena"].pending_clip = None       # a coefficient nobody consumed dies with the gradients it was computed for
         for g in self.param_groups:
             for p in g["params"]:
@@ -355,12 +436,16 @@ def flush_clip(arena):
     arena.pending_clip = None
     if pend is None:
         return
-    out, names = pend
+    out, names = pend[0], pend[1]
+    foreign = pend[2] if len(pend) > 2 else ()          # gradients of tensors outside the arena that the norm covered
+    names = frozenset(n for n in names if isinstance(n, str))
     if len(names) == sum(p.grad is not None for _, p in arena.param_list()) == len(arena.param_list()):
         arena.grad.mul_(out[1])
     else:
         for n in names:
             arena.view(n, "grad").mul_(out[1])
+    for g in foreign:
+        g.mul_(out[1])
 
 
 def clip_grad_norm_(parameters, max_norm, norm_type=2.0, defer_to_optimizer=None, pre_scale=1.0):
@@ -379,9 +464,14 @@ def clip_grad_norm_(parameters, max_norm, norm_type=2.0, defer_to_optimizer=None
     if owner is not None and not parameters.started and owner.__dict__.get("_arena") is not None:
         model, arena = owner, owner.materialize()          # the whole arena, no need to walk 600 tensors
         whole = True
+    foreign = []
     if model is None:
         params = [parameters] if isinstance(parameters, torch.Tensor) else list(parameters)
-        model, arena = _arena_of(params)
+        model, arena, foreign = _split_params(params)
+        if arena is None:
+            if not foreign:
+                raise RuntimeError("clip_grad_norm_: no parameters")
+            return _clip_foreign_only(foreign, max_norm, pre_scale)
         given = {p.data_ptr() for p in params}
     flush_clip(arena)                                       # two clips in a row: the first one's scaling is part of what the second measures
     # parameters without a gradient (frozen, or an unused head) are left out, as torch.nn.utils.clip_grad_norm_ does
@@ -395,8 +485,11 @@ def clip_grad_norm_(parameters, max_norm, norm_type=2.0, defer_to_optimizer=None
         if not (p.grad is g or p.grad.data_ptr() == g.data_ptr()):
             raise RuntimeError("clip_grad_norm_: the gradient of %s is not attached to the engine's arena (run backward first)" % n)
         have.append(n)
-    if not have:
+    if not have and not any(p.grad is not None for p in foreign):
         raise RuntimeError("clip_grad_norm_: gradients are not attached to the engine's arena (run backward first)")
+    flive = [p for p in foreign if p.grad is not None]
+    if flive and _red_mode(model) == "zero1":
+        raise NotImplementedError("clip_grad_norm_: data-parallel mode 'zero1' with parameters outside the model's arena")
     mask = None
     if len(have) != len(plist):
         cache = arena.__dict__.setdefault("_clip_masks", {})
@@ -418,6 +511,22 @@ def clip_grad_norm_(parameters, max_norm, norm_type=2.0, defer_to_optimizer=None
     if not hasattr(arena, "norm_chunks"):
         arena.norm_chunks = torch.zeros(npad + 256, device=arena.device)
     sums = arena.norm_chunks[:npad]
+    if flive:
+        # tensors outside the arena: one sum of squares each in the slots behind the chunk sums, then the same fixed-order sum over all
+        nf = len(flive)
+        npad = nchunks + nf + ((nchunks + nf) & 1)
+        buf = arena.__dict__.get("norm_slots")
+        if buf is None or buf.numel() < npad + 256:
+            buf = arena.__dict__["norm_slots"] = torch.zeros(npad + 256, device=arena.device)
+        sums = buf[:npad]
+        sums[nchunks + nf:].zero_()
+        ents = [(p, p.grad, None, None, 0) for p in flive]
+        for p in flive:
+            if p.grad.dtype != torch.float32 or not p.grad.is_contiguous() or p.grad.device != arena.device:
+                raise RuntimeError("clip_grad_norm_: the gradient of a tensor outside the arena must be a contiguous float32 tensor on %s" % arena.device)
+        flist, fmax = _tensor_list(ents, arena.device)
+        work = torch.empty(nf * L.lib.vk_grad_sqnorm_list_work_floats(), device=arena.device)
+        L.check(L.lib.vk_grad_sqnorm_list(L.ptr(flist), nf, fmax, L.ptr(work), L.ptr(sums[nchunks:]), L.stream_ptr()))
     out = torch.empty(2, device=arena.device)
     ddp = getattr(model, "_ddp", None)
     red = getattr(ddp, "reducer", None)
@@ -430,13 +539,37 @@ def clip_grad_norm_(parameters, max_norm, norm_type=2.0, defer_to_optimizer=None
     else:
         L.check(L.lib.vk_grad_sqnorm_chunks(L.ptr(arena.grad), 0, nchunks, L.ptr(mask), L.ptr(sums), L.stream_ptr()))
     L.check(L.lib.vk_grad_norm_from_chunks(L.ptr(sums), npad, pre_scale, float(max_norm), L.ptr(out), L.stream_ptr()))
-    names = frozenset(have)
+    names = frozenset(have + [("foreign", id(p)) for p in flive])
     if defer_to_optimizer is None:
         # the reference's plain call: defer when the optimizer that will consume these gradients is ours and steps exactly this set
         opt = getattr(arena, "_vk_adamw", None)
         opt = opt() if opt is not None else None
         defer_to_optimizer = opt is not None and opt._fused is not None and opt._fused["arena"] is arena and opt._grad_names() == names
-    arena.pending_clip = (out, names)
+    arena.pending_clip = (out, names, [p.grad for p in flive]) if flive else (out, names)
     if not defer_to_optimizer:
         flush_clip(arena)
+    return out[0]
+
+
+def _red_mode(model):
+    red = getattr(getattr(model, "_ddp", None), "reducer", None)
+    return red.mode if red is not None and (red.sharded or red.replicated) else None
+
+
+def _clip_foreign_only(params, max_norm, pre_scale):
+    """clip_grad_norm_ over torch tensors alone (no volta_amd model among them): the same kernels, applied at once."""
+    live = [p for p in params if p.grad is not None]
+    if not live:
+        raise RuntimeError("clip_grad_norm_: no parameter carries a gradient")
+    dev = live[0].device
+    nf = len(live)
+    npad = nf + (nf & 1)
+    sums = torch.zeros(npad + 256, device=dev)
+    flist, fmax = _tensor_list([(p, p.grad, None, None, 0) for p in live], dev)
+    work = torch.empty(nf * L.lib.vk_grad_sqnorm_list_work_floats(), device=dev)
+    L.check(L.lib.vk_grad_sqnorm_list(L.ptr(flist), nf, fmax, L.ptr(work), L.ptr(sums), L.stream_ptr()))
+    out = torch.empty(2, device=dev)
+    L.check(L.lib.vk_grad_norm_from_chunks(L.ptr(sums), npad, pre_scale, float(max_norm), L.ptr(out), L.stream_ptr()))
+    for p in live:
+        p.grad.mul_(out[1])
     return out[0]
