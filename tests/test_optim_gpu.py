@@ -182,9 +182,8 @@ def test_pipelined_adamw_under_the_next_forward_changes_nothing():
         results.append(([[float(x) for x in l] for l in losses], model._arena.master.clone(), opt._fused["m"].clone(), model._arena.shadow.clone()))
     (l0, p0, m0, s0), (l1, p1, m1, s1) = results
     assert all(_same(a, b, 1e-5) for a, b in zip(l0, l1)), (l0, l1)
-    # word-embedding rows: checked to a last-bit tolerance; everything else is bit-identical
-    assert float((p0 - p1).abs().max()) <= 1e-5 and float((m0 - m1).abs().max()) <= 1e-5
-    assert float((s0.float() - s1.float()).abs().max()) <= 1e-2
+    # the loss values above sum their rows with atomics; no gradient reads them, so the parameters, moments and bf16 copies are bit-identical
+    assert torch.equal(p0, p1) and torch.equal(m0, m1) and torch.equal(s0, s1)
     assert l0[0] != l0[-1]                                             # the model did move
 
 

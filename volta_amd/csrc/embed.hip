@@ -77,7 +77,7 @@ __global__ __launch_bounds__(256) void embed_scatter_kernel(vk_embed_bwd_args a,
         row_s[threadIdx.x] = row;
         id_s[threadIdx.x] = row >= 0 ? clampi(a.ids[row], a.V) : -1;
         ty_s[threadIdx.x] = (row >= 0 && a.type_ids) ? (int)clampi(a.type_ids[row], a.n_types) : 0;
-        ps_s[threadIdx.x] = (row >= 0 && a.pos_ids) ? clampi(a.pos_ids[row], a.P) : -1;
+        ps_s[threadIdx.x] = (row >= 0 && a.pos_ids && w.Pp) ? clampi(a.pos_ids[row], a.P) : -1;   // no position workspace: dpos is NULL
     }
     __syncthreads();
     if (threadIdx.x < 32) {
