@@ -497,6 +497,36 @@ int vk_adamw_step_list(const vk_adamw_args* a, const vk_adamw_tensor* list, int 
  * chunk sums for vk_grad_norm_from_chunks.  work: n * vk_grad_sqnorm_list_work_floats() floats of scratch. */
 int vk_grad_sqnorm_list(const vk_adamw_tensor* list, int n, int64_t max_numel, float* work, float* sums, vk_stream_t s);
 int vk_grad_sqnorm_list_work_floats(void);
+/* Fused RAdam (volta_amd/csrc/radam.hip) replaces volta.optimization.RAdam.step and PlainRAdam.step (volta/optimization.py:18-93,
+ * :103-169; train_task.py:27,227-228, `--optim RAdam`).  Per element, in fp32, with g pre-multiplied by grad_scale * clip[1]
+ * (volta/optimization.py:48-91):
+ *   v = b2 v + (1-b2) g^2 ; m = b1 m + (1-b1) g ; p -= decay_c p ; p -= step_c m / (sqrt(v) + eps)  if rect_c, else  p -= step_c m
+ * The host decides each class c: decay_c = weight_decay * group lr (applied BEFORE the update, :83-84), step_c = the step size the
+ * reference's shared 10-slot `buffer` yields for that parameter (:51-80; PlainRAdam: its own group lr), rect_c = N_sma >= 5.  Classes
+ * come from (group lr, weight decay, step count): step counts differ once a parameter has missed a gradient.  chunk_class[i] selects the
+ * class of 1024-element chunk i (NULL: class 0); VK_CHUNK_SKIP (and any class >= VK_RADAM_CLASSES) leaves the chunk untouched.  Same
+ * arenas, offsets and bf16 shadow refresh as vk_adamw_step. */
+#define VK_RADAM_CLASSES 64
+typedef struct vk_radam_args {
+    float* p;
+    const float* g;
+    float* m;
+    float* v;
+    void* shadow;               /* bf16 copy of p, refreshed in the same pass, or NULL */
+    const uint8_t* chunk_class; /* [n / 1024] or NULL (class 0) */
+    const float* clip;          /* device float[2] from the gradient-norm kernels or NULL */
+    int64_t n;                  /* arena length, a multiple of 1024 */
+    float cls_decay[VK_RADAM_CLASSES];
+    float cls_step[VK_RADAM_CLASSES];
+    int32_t cls_rect[VK_RADAM_CLASSES];
+    float beta1, beta2;
+    float one_minus_beta1, one_minus_beta2;   /* 1 - beta rounded from double, as the reference's torch calls round it */
+    float eps, grad_scale;
+} vk_radam_args;
+int vk_radam_step(const vk_radam_args* a, vk_stream_t s);
+/* The same element function over `n` device descriptors of fp32 tensors OUTSIDE the arena (a torch head on a standalone BertModel) in ONE
+ * launch; descriptor cls selects the class.  a->p / g / m / v / shadow / chunk_class / n are ignored; max_numel sizes the grid. */
+int vk_radam_step_list(const vk_radam_args* a, const vk_adamw_tensor* list, int n, int64_t max_numel, vk_stream_t s);
 int vk_axpy_f32(float* y, const float* x, float alpha, int64_t n, vk_stream_t s);
 /* dst[i] = sum_{s < nslabs} src[s * slab_stride + i], i < n (fp32).  Combines the partial weight gradients of a
  * split-K wgrad: each K-chunk is an ordinary problem of the grouped TN launch writing its own slab. */

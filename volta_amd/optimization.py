@@ -2,6 +2,8 @@
 
   AdamW                  pytorch_transformers.optimization.AdamW  (same constructor / param-group semantics)
   WarmupLinearSchedule   pytorch_transformers.optimization.WarmupLinearSchedule
+  RAdam, PlainRAdam      volta.optimization.RAdam / PlainRAdam  (train_task.py:27,227-228; see RAdam)
+  WarmupConstantSchedule pytorch_transformers.optimization.WarmupConstantSchedule  (train_task.py:24,233-234)
   clip_grad_norm_        torch.nn.utils.clip_grad_norm_
 
 All parameters of a volta_amd model are views of one flat arena, so `step()` is ONE fused kernel over
@@ -12,6 +14,7 @@ import ctypes as C
 import math
 import os
 
+import numpy as np
 import torch
 import weakref
 
@@ -416,6 +419,342 @@ class AdamW(Optimizer):
                     p.grad.zero_()
 
 
+def _radam_step_size(lr, t, beta1, beta2):
+    """(step_size, N_sma) of step t in the reference's own expression order (volta/optimization.py:57-78, :143-165), in Python floats."""
+    beta2_t = beta2 ** t
+    N_sma_max = 2 / (1 - beta2) - 1
+    N_sma = N_sma_max - 2 * t * beta2_t / (1 - beta2_t)
+    if N_sma >= 5:
+        step_size = (lr * math.sqrt((1 - beta2_t) * (N_sma - 4) / (N_sma_max - 4) * (N_sma - 2) / N_sma * N_sma_max / (N_sma_max - 2))
+                     / (1 - beta1 ** t))
+    else:
+        step_size = lr / (1 - beta1 ** t)
+    return step_size, N_sma
+
+
+def radam_runs(steps, live, lr_of, uniform=None):
+    """The stepping parameters of one RAdam step as runs of equal step count, in param_groups order.  steps[i]: parameter i's step count
+    before this step, live[i]: it has a gradient, lr_of(i): its group's lr now.  Returns (runs, run_of): runs = [(t, lr of the run's first
+    parameter)] with t the count after this step; run_of[i] = the run of parameter i, -1 when it does not step.  Within a run only the first
+    parameter can miss the reference's buffer: every later one finds the slot it filled.  `uniform`: the common count, when the caller
+    knows every parameter has it -- with every parameter live that is one run, found without a walk (run_of None: all in run 0)."""
+    if uniform is not None and all(live):
+        return [(uniform + 1, lr_of(0))], None
+    runs, run_of, prev = [], [-1] * len(steps), None
+    for i, t in enumerate(steps):
+        if not live[i]:
+            continue
+        t += 1
+        if t != prev:
+            runs.append((t, lr_of(i)))
+            prev = t
+        run_of[i] = len(runs) - 1
+    return runs, run_of
+
+
+def radam_plan(buffer, runs, beta1, beta2):
+    """The reference RAdam's shared step-size cache (volta/optimization.py:12,51-80) over `runs` (radam_runs): per run (step_size,
+    rectified), `buffer` (10 slots [step, N_sma, step_size], slot = step % 10) updated in place exactly as the reference's loop leaves it.
+    The first parameter to reach step t with slot t % 10 not holding t computes the step size from ITS group's lr and stores it; every
+    later parameter at step t reuses it (another group's lr), until a different step count claims the slot."""
+    out = []
+    for t, lr in runs:
+        b = buffer[int(t % 10)]
+        if t == b[0]:
+            N_sma, step_size = b[1], b[2]
+        else:
+            step_size, N_sma = _radam_step_size(lr, t, beta1, beta2)
+            b[0], b[1], b[2] = t, N_sma, step_size
+        out.append((step_size, N_sma >= 5))
+    return out
+
+
+class RAdam(Optimizer):
+    """volta.optimization.RAdam (train_task.py:27,227-228, `--optim RAdam`): same constructor, param-group semantics, `buffer` and
+    state_dict layout; one fused launch over the arena (vk_radam_step) plus one over tensors outside it (vk_radam_step_list) per step.
+
+    Reference semantics kept on purpose: all parameters share the 10-slot step-size cache `self.buffer` (radam_plan), so the step size of
+    a parameter can come from another group's lr; only the decay `-weight_decay * lr * p`, applied BEFORE the update, uses the group's own
+    lr.  A parameter without a gradient is skipped and its step count stays behind.  Accepts one volta_amd model's parameters plus
+    contiguous CUDA fp32 tensors, as AdamW does; clip_grad_norm_ defers its coefficient to this optimizer's next step the same way.
+    Out of scope (raise): DistributedDataParallel(mode="zero1") (NotImplementedError), groups with different betas or eps (RuntimeError),
+    and there is no overlap_with_forward form."""
+    _plain = False
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0):
+        if lr < 0.0:
+            raise ValueError("Invalid learning rate: {} - should be >= 0.0".format(lr))
+        if not 0.0 <= betas[0] < 1.0:
+            raise ValueError("Invalid beta parameter: {} - should be in [0.0, 1.0[".format(betas[0]))
+        if not 0.0 <= betas[1] < 1.0:
+            raise ValueError("Invalid beta parameter: {} - should be in [0.0, 1.0[".format(betas[1]))
+        if not 0.0 <= eps:
+            raise ValueError("Invalid epsilon value: {} - should be >= 0.0".format(eps))
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+        if not self._plain:
+            self.buffer = [[None, None, None] for _ in range(10)]
+        self._hyper()
+        self._fused = None
+        self._pending = None        # a state loaded before the model was on the GPU (train_task.py:236-246): applied at the first setup
+        try:                        # clip_grad_norm_ defers to this optimizer (see AdamW.__init__)
+            _, arena, _ = _split_params([p for g in self.param_groups for p in g["params"]])
+            if arena is not None:
+                arena._vk_adamw = weakref.ref(self)
+        except RuntimeError:
+            pass
+
+    def _name(self):
+        return "volta_amd." + type(self).__name__
+
+    def _hyper(self):
+        """(beta1, beta2, eps) common to all groups: one launch steps all of them."""
+        hs = {(tuple(g["betas"]), g["eps"]) for g in self.param_groups}
+        if len(hs) != 1:
+            raise RuntimeError("%s: betas / eps must be common to all groups (got %s)" % (self._name(), sorted(hs)))
+        (b1, b2), eps = hs.pop()
+        return float(b1), float(b2), float(eps)
+
+    def _setup(self):
+        allp = [p for g in self.param_groups for p in g["params"]]
+        labels = ["param_groups[%d]['params'][%d]" % (gi, i) for gi, g in enumerate(self.param_groups) for i in range(len(g["params"]))]
+        model, arena, foreign = _split_params(allp, labels)
+        if arena is None and not foreign:
+            raise RuntimeError("%s: no parameters" % self._name())
+        byptr = {p.data_ptr(): n for n, p in arena.params.items()} if arena is not None else {}
+        fids = {id(p) for p in foreign}
+        ents = []                   # per parameter in param_groups order: (group index, arena name or None, chunk range, foreign record)
+        for gi, g in enumerate(self.param_groups):
+            for p in g["params"]:
+                if id(p) in fids:
+                    ents.append((gi, p, None, 0, 0, dict(p=p, m=torch.zeros_like(p), v=torch.zeros_like(p))))
+                else:
+                    n = byptr[p.data_ptr()]
+                    c0, c1 = _chunks_of(arena, n)
+                    ents.append((gi, p, n, c0, c1, None))
+        f = dict(model=model, arena=arena, ents=ents, steps=[0] * len(ents), uniform=0, masks={})
+        if arena is not None:
+            arena._vk_adamw = weakref.ref(self)
+            f.update(m=torch.zeros_like(arena.master), v=torch.zeros_like(arena.master))
+        self._fused = f
+        if self._pending is not None:
+            self._apply_state(self._pending)
+            self._pending = None
+
+    def _grad_names(self):
+        """Names of this optimizer's parameters that carry a gradient now (what a deferred clip coefficient must have been computed over)."""
+        return frozenset(n if n is not None else ("foreign", id(p)) for _, p, n, _, _, _ in self._fused["ents"] if p.grad is not None)
+
+    def _plan(self, live, b1, b2):
+        """Per parameter: (step_size, rectified), or None for a parameter that does not step.  RAdam: the shared buffer (radam_plan);
+        PlainRAdam: each parameter's own group lr and step count (volta/optimization.py:143-165)."""
+        f, groups, ents = self._fused, self.param_groups, self._fused["ents"]
+        lr_of = lambda i: groups[ents[i][0]]["lr"]
+        if self._plain:
+            memo = {}
+            out = []
+            for i, t in enumerate(f["steps"]):
+                if not live[i]:
+                    out.append(None)
+                    continue
+                key = (lr_of(i), t + 1)
+                if key not in memo:
+                    ss, N_sma = _radam_step_size(key[0], key[1], b1, b2)
+                    memo[key] = (ss, N_sma >= 5)
+                out.append(memo[key])
+            return out
+        runs, run_of = radam_runs(f["steps"], live, lr_of, f["uniform"])
+        plan = radam_plan(self.buffer, runs, b1, b2)
+        if run_of is None:
+            return [plan[0]] * len(live)
+        return [plan[r] if r >= 0 else None for r in run_of]
+
+    def _chunk_map(self, cls_of):
+        """Device chunk-class bytes for the arena parameters' classes (cached by the class tuple: a steady run reuses one map)."""
+        f = self._fused
+        arena = f["arena"]
+        key = tuple(c for (_, _, n, _, _, _), c in zip(f["ents"], cls_of) if n is not None)
+        cc = f["masks"].get(key)
+        if cc is None:
+            own = np.full(arena.total // 1024, -1, dtype=np.int16)
+            for (_, _, n, c0, c1, _), c in zip(f["ents"], cls_of):
+                if n is None:
+                    continue
+                for e in {c0, c1 - 1}:
+                    if own[e] not in (-1, c):
+                        raise RuntimeError("%s: parameters sharing an arena chunk (the fused query / key / value slot) must step together with "
+                                           "the same lr, weight decay and step count (%s, chunk %d)" % (self._name(), n, e))
+                own[c0:c1] = c
+            own[own < 0] = L.CHUNK_SKIP
+            if len(f["masks"]) > 16:
+                f["masks"].clear()
+            cc = f["masks"][key] = torch.from_numpy(own.astype(np.uint8)).to(arena.device)
+        return cc
+
+    @torch.no_grad()
+    def step(self, closure=None, grad_scale=1.0):
+        loss = closure() if closure is not None else None
+        if self._fused is None:
+            self._setup()
+        f = self._fused
+        arena, ents = f["arena"], f["ents"]
+        red = getattr(getattr(f["model"], "_ddp", None), "reducer", None)
+        if red is not None and red.mode == "zero1":
+            raise NotImplementedError("%s: data-parallel mode 'zero1' shards the optimizer state for AdamW only; use mode 'allreduce' or "
+                                      "'rs_ag'" % self._name())
+        b1, b2, eps = self._hyper()
+        live = []
+        for gi, p, n, _, _, _ in ents:
+            g = p.grad
+            live.append(g is not None)
+            if g is None:
+                continue
+            if n is not None:
+                if g.data_ptr() != arena.grad.data_ptr() + 4 * arena.offset[n]:
+                    raise RuntimeError("%s: the gradient of %s is not the engine's arena view (a foreign tensor was assigned to .grad); run "
+                                       "backward through the model, or zero_grad(set_to_none=True)" % (self._name(), n))
+            elif g.dtype != torch.float32 or not g.is_contiguous() or g.shape != p.shape or g.device != p.device:
+                raise RuntimeError("%s: the gradient of a tensor outside the arena must be a contiguous float32 tensor of its shape" % self._name())
+        if not any(live):
+            return loss
+        plan = self._plan(live, b1, b2)
+        # classes: (decay = weight_decay * group lr, step size, rectified); the kernels look them up by class index
+        classes, cls_of = {}, []
+        for (gi, _, _, _, _, _), pl in zip(ents, plan):
+            if pl is None:
+                cls_of.append(L.CHUNK_SKIP)
+                continue
+            g = self.param_groups[gi]
+            key = (g["weight_decay"] * g["lr"], pl[0], bool(pl[1]))
+            if key not in classes:
+                if len(classes) == L.RADAM_CLASSES:
+                    raise RuntimeError("%s: more than %d distinct (lr, weight decay, step count) classes in one step" % (self._name(), L.RADAM_CLASSES))
+                classes[key] = len(classes)
+            cls_of.append(classes[key])
+        a = L.RadamArgs()
+        for (decay, ss, rect), c in classes.items():
+            a.cls_decay[c], a.cls_step[c], a.cls_rect[c] = decay, ss, int(rect)
+        a.beta1, a.beta2, a.one_minus_beta1, a.one_minus_beta2, a.eps, a.grad_scale = b1, b2, 1 - b1, 1 - b2, eps, grad_scale
+        clip = None
+        if arena is not None:
+            pend = getattr(arena, "pending_clip", None)
+            if pend is not None:
+                if pend[1] == self._grad_names():
+                    clip = pend[0]             # computed over exactly the gradients this step consumes: folded into the pass
+                else:
+                    flush_clip(arena)
+            arena.pending_clip = None
+            a.clip = clip.data_ptr() if clip is not None else None
+            if any(l and e[2] is not None for l, e in zip(live, ents)):
+                a.p, a.g, a.m, a.v = arena.master.data_ptr(), arena.grad.data_ptr(), f["m"].data_ptr(), f["v"].data_ptr()
+                a.shadow, a.chunk_class, a.n = arena.shadow.data_ptr(), self._chunk_map(cls_of).data_ptr(), arena.total
+                arena.sync_optimizer()
+                L.check(L.lib.vk_radam_step(C.byref(a), L.stream_ptr()))
+                arena.mark_shadow_fresh()
+        flive = [(e[5]["p"], e[5]["p"].grad, e[5]["m"], e[5]["v"], c) for l, e, c in zip(live, ents, cls_of) if l and e[2] is None]
+        if flive:
+            key = tuple((p.data_ptr(), g.data_ptr(), c) for p, g, _, _, c in flive)
+            if f.get("flist_key") != key:
+                f["flist"], f["flist_max"] = _tensor_list(flive, flive[0][0].device)
+                f["flist_key"] = key
+            L.check(L.lib.vk_radam_step_list(C.byref(a), L.ptr(f["flist"]), len(flive), f["flist_max"], L.stream_ptr()))
+        steps = f["steps"]
+        if f["uniform"] is not None and all(live):
+            f["uniform"] += 1
+            for i in range(len(steps)):
+                steps[i] += 1
+        else:
+            for i, l in enumerate(live):
+                steps[i] += l
+            f["uniform"] = steps[0] if steps and all(t == steps[0] for t in steps) else None
+        return loss
+
+    def zero_grad(self, set_to_none=True):
+        if self._fused is not None and self._fused["arena"] is not None:
+            self._fused["arena"].pending_clip = None
+        for g in self.param_groups:
+            for p in g["params"]:
+                if set_to_none:
+                    p.grad = None
+                elif p.grad is not None:
+                    p.grad.zero_()
+
+    def synchronize(self):
+        if self._fused is not None and self._fused["arena"] is not None:
+            self._fused["arena"].sync_optimizer()
+
+    # ---- checkpoints: the reference's layout, {"step", "exp_avg", "exp_avg_sq"} per parameter that has stepped, indexed in param_groups
+    # order; `buffer` is not part of it (volta/optimization.py keeps it outside `state`), so it starts empty after a load
+    def state_dict(self):
+        self.synchronize()
+        sd = super().state_dict()
+        f = self._fused
+        if f is None:
+            sd["state"] = {i: {k: (v.clone() if torch.is_tensor(v) else v) for k, v in st.items()} for i, st in (self._pending or {}).items()}
+            return sd
+        out = {}
+        for i, ((_, p, n, _, _, fr), t) in enumerate(zip(f["ents"], f["steps"])):
+            if t == 0:
+                continue
+            if fr is not None:
+                m, v = fr["m"].clone(), fr["v"].clone()
+            else:
+                o, k = f["arena"].offset[n], p.numel()
+                m, v = f["m"][o:o + k].view(p.shape).clone(), f["v"][o:o + k].view(p.shape).clone()
+            out[i] = {"step": t, "exp_avg": m, "exp_avg_sq": v}
+        sd["state"] = out
+        return sd
+
+    def load_state_dict(self, state_dict):
+        self.synchronize()
+        state = state_dict.get("state", {})
+        super().load_state_dict({"state": {}, "param_groups": state_dict["param_groups"]})
+        self._hyper()
+        if not self._plain:
+            self.buffer = [[None, None, None] for _ in range(10)]
+        allp = [p for g in self.param_groups for p in g["params"]]
+        st = {}
+        for k, s in state.items():
+            i = int(k)
+            if not 0 <= i < len(allp):
+                raise ValueError("%s.load_state_dict: state for parameter %d, the optimizer has %d" % (self._name(), i, len(allp)))
+            if int(s["step"]) < 1 or s["exp_avg"].numel() != allp[i].numel() or s["exp_avg_sq"].numel() != allp[i].numel():
+                raise ValueError("%s.load_state_dict: parameter %d's state does not fit it (step %s, %d / %d elements for %d)"
+                                 % (self._name(), i, s["step"], s["exp_avg"].numel(), s["exp_avg_sq"].numel(), allp[i].numel()))
+            st[i] = {"step": int(s["step"]), "exp_avg": s["exp_avg"].detach().float().cpu().clone(),
+                     "exp_avg_sq": s["exp_avg_sq"].detach().float().cpu().clone()}
+        if self._fused is None and not all(p.device.type == "cuda" for p in allp):
+            self._pending = st          # the model is not on the GPU yet (train_task.py: resume() before model.to(device))
+            return
+        if self._fused is None:
+            self._setup()
+        self._apply_state(st)
+
+    def _apply_state(self, st):
+        f = self._fused
+        for i, (_, p, n, _, _, fr) in enumerate(f["ents"]):
+            s = st.get(i)
+            m = s["exp_avg"].reshape(-1) if s is not None else 0.0
+            v = s["exp_avg_sq"].reshape(-1) if s is not None else 0.0
+            if fr is not None:
+                dm, dv = fr["m"].view(-1), fr["v"].view(-1)
+            else:
+                o, k = f["arena"].offset[n], p.numel()
+                dm, dv = f["m"][o:o + k], f["v"][o:o + k]
+            if s is None:
+                dm.zero_(); dv.zero_()
+            else:
+                dm.copy_(m); dv.copy_(v)
+            f["steps"][i] = s["step"] if s is not None else 0
+        steps = f["steps"]
+        f["uniform"] = steps[0] if steps and all(t == steps[0] for t in steps) else None
+
+
+class PlainRAdam(RAdam):
+    """volta.optimization.PlainRAdam (volta/optimization.py:96-169): RAdam with each parameter's step size from its own group's lr and
+    step count, and no shared buffer.  Same kernels, same scope."""
+    _plain = True
+
+
 class WarmupLinearSchedule(LambdaLR):
     """Linear warm-up from 0 to 1 over `warmup_steps`, then linear decay to 0 at `t_total`."""
 
@@ -428,6 +767,19 @@ class WarmupLinearSchedule(LambdaLR):
         if step < self.warmup_steps:
             return float(step) / float(max(1, self.warmup_steps))
         return max(0.0, float(self.t_total - step) / float(max(1.0, self.t_total - self.warmup_steps)))
+
+
+class WarmupConstantSchedule(LambdaLR):
+    """Linear warm-up from 0 to 1 over `warmup_steps`, then 1 (pytorch_transformers 1.1.0; train_task.py:233-234, the default schedule)."""
+
+    def __init__(self, optimizer, warmup_steps, last_epoch=-1):
+        self.warmup_steps = warmup_steps
+        super().__init__(optimizer, self.lr_lambda, last_epoch=last_epoch)
+
+    def lr_lambda(self, step):
+        if step < self.warmup_steps:
+            return float(step) / float(max(1.0, self.warmup_steps))
+        return 1.0
 
 
 def flush_clip(arena):
