@@ -340,6 +340,24 @@ typedef struct vk_grad_seed_args {
     int32_t B, L, H, row0, ld, ldy, accumulate, reserved_;
 } vk_grad_seed_args;
 int vk_grad_seed(const vk_grad_seed_args* a, vk_stream_t s);
+/* Pair gather of the retrieval scorer (volta_amd/retrieval.py): eval_retrieval.py:172-191 repeats each caption and sends the same images
+ * through the whole model once per caption; the scorer computes the modality-only prefixes once per item and builds the mixing suffix's
+ * per-pair inputs here.  Segment k copies bytes[k] (a positive multiple of 4) per pair from item c (side 0, caption) or item i (side 1,
+ * image) of src[k] (item stride bytes[k]) to pair p of dst[k].  Pairs: cap_idx / img_idx (int64 [npairs], both set), or the cross product
+ * p -> (c0 + p / ni, i0 + p % ni) with npairs = nc * ni, checked against n_items on the host.  An explicit index outside [0, n_items[side])
+ * zero-fills its block.  One launch for all segments. */
+#define VK_PAIR_MAX_SEGS 8
+typedef struct vk_pair_gather_args {
+    const void* src[VK_PAIR_MAX_SEGS];
+    void* dst[VK_PAIR_MAX_SEGS];
+    int64_t bytes[VK_PAIR_MAX_SEGS];
+    int32_t side[VK_PAIR_MAX_SEGS];
+    const int64_t* cap_idx;
+    const int64_t* img_idx;
+    int64_t n_items[2];
+    int32_t nseg, npairs, c0, nc, i0, ni;
+} vk_pair_gather_args;
+int vk_pair_gather(const vk_pair_gather_args* a, vk_stream_t s);
 
 /* ------------------------------------------------------------------------------------------------
  * Heads and losses, evaluated on labelled rows only.  Replaces BertPreTrainingHeads + the loss code of

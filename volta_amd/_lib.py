@@ -145,6 +145,15 @@ class GradSeedArgs(C.Structure):
                 ("row0", i32), ("ld", i32), ("ldy", i32), ("accumulate", i32), ("reserved_", i32)]
 
 
+PAIR_MAX_SEGS = 8         # VK_PAIR_MAX_SEGS
+
+
+class PairGatherArgs(C.Structure):
+    _fields_ = [("src", c_p * PAIR_MAX_SEGS), ("dst", c_p * PAIR_MAX_SEGS), ("bytes", C.c_int64 * PAIR_MAX_SEGS), ("side", i32 * PAIR_MAX_SEGS),
+                ("cap_idx", c_p), ("img_idx", c_p), ("n_items", C.c_int64 * 2), ("nseg", i32), ("npairs", i32), ("c0", i32), ("nc", i32),
+                ("i0", i32), ("ni", i32)]
+
+
 class TailJob(C.Structure):
     _fields_ = [("dst", c_p), ("dst2", c_p), ("src", c_p), ("src2", c_p), ("stride", C.c_int64), ("n", C.c_int64), ("kind", i32), ("count", i32),
                 ("accumulate", i32), ("block_start", i32)]
@@ -265,6 +274,7 @@ _sig("vk_adamw_step_list", C.c_int, C.POINTER(AdamwArgs), c_p, C.c_int, C.c_int6
 _sig("vk_grad_sqnorm_list", C.c_int, c_p, C.c_int, C.c_int64, c_p, c_p, c_p)
 _sig("vk_grad_sqnorm_list_work_floats", C.c_int)
 _sig("vk_grad_seed", C.c_int, C.POINTER(GradSeedArgs), c_p)
+_sig("vk_pair_gather", C.c_int, C.POINTER(PairGatherArgs), c_p)
 _sig("vk_radam_step", C.c_int, C.POINTER(RadamArgs), c_p)
 _sig("vk_radam_step_list", C.c_int, C.POINTER(RadamArgs), c_p, C.c_int, C.c_int64, c_p)
 _sig("vk_grad_sqnorm_chunks", C.c_int, c_p, C.c_int64, C.c_int64, c_p, c_p, c_p)
@@ -299,7 +309,7 @@ EXPORTS = ["vk_version", "vk_device_arch", "vk_last_error", "vk_set_seed", "vk_c
            "vk_relu_bwd_bf16", "vk_copy_async", "vk_select_rows", "vk_gather_rows", "vk_scatter_rows_add", "vk_xent_fwd",
            "vk_xent_bwd", "vk_kl_fwd", "vk_kl_bwd", "vk_loss_finalize", "vk_pool_mul_fwd", "vk_pool_mul_bwd",
            "vk_pool_fuse_fwd", "vk_pool_fuse_bwd", "vk_text_end_rows", "vk_vlbert_obj_ids", "vk_vlbert_positions", "vk_vis_loss_fwd", "vk_vis_loss_bwd", "vk_nce_negatives",
-           "vk_mask_prep", "vk_mul_bf16", "vk_grad_norm_workspace_floats", "vk_grad_norm_clip", "vk_grad_norm_clip_masked", "vk_grad_sqnorm_chunks", "vk_grad_norm_from_chunks", "vk_adamw_step", "vk_adamw_step_on", "vk_adamw_step_list", "vk_grad_sqnorm_list", "vk_grad_sqnorm_list_work_floats", "vk_grad_seed", "vk_radam_step", "vk_radam_step_list",
+           "vk_mask_prep", "vk_mul_bf16", "vk_grad_norm_workspace_floats", "vk_grad_norm_clip", "vk_grad_norm_clip_masked", "vk_grad_sqnorm_chunks", "vk_grad_norm_from_chunks", "vk_adamw_step", "vk_adamw_step_on", "vk_adamw_step_list", "vk_grad_sqnorm_list", "vk_grad_sqnorm_list_work_floats", "vk_grad_seed", "vk_pair_gather", "vk_radam_step", "vk_radam_step_list",
            "vk_axpy_f32", "vk_sum_slabs_f32", "vk_sum_slabs_bf16", "vk_memset_async", "vk_hold_cus", "vk_gate_wait", "vk_bump_u64", "vk_store_u64", "vk_gate_value", "vk_comm_standin", "vk_gemm_reserve_cus", "vk_side_tail", "vk_run_ops", "vk_run_ops_timed", "vk_side_join", "vk_side_join_from", "vk_side_stream", "vk_side_enable", "vk_concap_batch",
            "vk_lmdb_open", "vk_lmdb_close", "vk_lmdb_entries", "vk_lmdb_first", "vk_lmdb_next", "vk_lmdb_get", "vk_concap_record_decode", "vk_concap_records_decode", "vk_b64_decode",
            "vk_wordpiece_open", "vk_wordpiece_close", "vk_wordpiece_vocab_size", "vk_wordpiece_token_id", "vk_wordpiece_encode", "vk_wordpiece_encode_batch"]

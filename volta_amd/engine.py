@@ -235,14 +235,23 @@ class StepEngine:
 
     H8_MUL = 8.0           # static scale of the fp8 copy of the GELU output: |h| <= 56 representable, 2^-9 absolute resolution near 0
 
-    def __init__(self, cfg, arena, B, T, Rv, train, heads="pretrain", fp8=False, task=None, task_dropout=0.1, attn_maps=False):
+    def __init__(self, cfg, arena, B, T, Rv, train, heads="pretrain", fp8=False, task=None, task_dropout=0.1, attn_maps=False, part=None, split=None):
         """fp8: the forward Q|K|V, FFN-up and FFN-down projections of every sub-layer run on the e4m3 MFMA path (csrc/fp8.hip); inputs are
         quantised per row right before the GEMM, weights per output channel whenever they change; the backward stays bf16.
         heads: "pretrain" = the three pre-training heads and losses (BertForVLPreTraining); "tasks" = poolers only, the
         sequence and pooled outputs leave the engine and their gradients enter it (BertForVLTasks); "backbone" = the "tasks" plan without a
-        task, its backward seeded from outside: d(loss)/d(every returned state) enters through `bind_grads` (BertModel on its own)."""
+        task, its backward seeded from outside: d(loss)/d(every returned state) enters through `bind_grads` (BertModel on its own);
+        "score" = one forward-only list of the retrieval scorer (volta_amd/retrieval.py), eval semantics, no backward: `part` "text" (text
+        embedding + the text-only sub-layers, B captions), "image" (image embedding + the vision-only sub-layers, B images) or "pair" (the
+        mixing suffix on B pairs whose inputs vk_pair_gather wrote into `pair_inputs`, poolers, fusion and the scoring head: `task`'s
+        VL-logit classifier, or cls.bi_seq_relationship when task is None); `split` = retrieval.split_plan(cfg)."""
         self.cfg, self.arena, self.B, self.T, self.Rv, self.train = cfg, arena, B, T, Rv, train
         self.heads = heads
+        self.part, self.split = part, split
+        self.fwd_only = heads == "score"   # the builders return before their backward part
+        self.only = None                   # score prefixes: the one stream (0 text, 1 vision) whose problems a sub-layer emits
+        if self.fwd_only and (train or fp8 or attn_maps or part not in ("text", "image", "pair") or split is None):
+            raise ValueError("a score plan is an eval-mode bf16 forward of part text | image | pair with a split plan")
         self.task = task              # heads == "tasks": (task id, its task_cfg entry) -- the classifier built behind the poolers
         self.attn_maps = bool(attn_maps)      # keep every attention sub-layer's probabilities (config.visualization, encoders.py:342-358): generic attention kernels
         self.attn_map_info = []
@@ -532,6 +541,8 @@ class StepEngine:
 
     # ---------------------------------------------------------------- build
     def _build(self):
+        if self.fwd_only:
+            return self._build_score()
         cfg, B, H = self.cfg, self.B, self.H
         st = self.st
         f = self.fwd.ops
@@ -639,6 +650,107 @@ class StepEngine:
         self.fwd.freeze()
         self.bwd.freeze()
 
+    def _build_score(self):
+        """heads == "score" (volta_amd/retrieval.py): the existing builders, forward part only.  A prefix list runs one stream at B items;
+        the pair list starts from per-pair buffers (`pair_inputs`: [(input name, tensor, side 0 caption | 1 image)], filled by one
+        vk_pair_gather launch ahead of the list) and ends in `score_out`, fp32 logits [B, 64]."""
+        cfg, B, T, Rv = self.cfg, self.B, self.T, self.Rv
+        f = self.fwd.ops
+        text_subs, vision_subs, per_modality = self.split
+        kinds = dict(sublayer_schedule(cfg))
+        self.x, self.x8, self.level, self.bwd_pro = [None, None], [None, None], [0, 0], []
+        self.masks = [self.buf("mask_t", (B, T), torch.float32), self.buf("mask_v", (B, Rv), torch.float32)]
+        kind = cfg.image_embeddings
+
+        def mask_prep(m, src=None):
+            g = self.generic(L.FN_MASK_PREP, p=(src, self.masks[m]), n=(B * self.st[m].L,))
+            if src is None:
+                self.patch(("attention_mask", "image_attention_mask")[m], g, "p", 0)
+            f.append((L.OP_GENERIC, 0, 0, 0, g, None, None))
+
+        def sublayers(ns):
+            for n in ns:
+                self._attn_sublayer(n) if kinds[n] == "attn" else self._ffn_sublayer(n)
+
+        if self.part in ("text", "image"):
+            m = 0 if self.part == "text" else 1
+            subs = text_subs if m == 0 else vision_subs
+            if not per_modality:
+                raise ValueError("image_embeddings=%r mixes the modalities in its embedding: there is no per-modality prefix" % kind)
+            if subs:
+                mask_prep(m)
+            if m == 0:
+                self._emb_text("bert.embeddings.")
+            elif kind == "uniter":
+                self._emb_image_uniter("bert.embeddings.")
+            else:
+                (self._emb_image_vilbert if kind == "vilbert" else self._emb_image_lxmert)("bert.v_embeddings.")
+            self.only = m
+            sublayers(subs)
+            self.only = None
+            self.score_out = self.x[m]
+        else:
+            i64, f32 = torch.int64, torch.float32
+            raw = [self.buf("pair_mask_t", (B, T), i64), self.buf("pair_mask_v", (B, Rv), i64)]
+            if per_modality:
+                ins = [("x_t", self.buf("pair_x_t", (B * T, self.st[0].H)), 0), ("x_v", self.buf("pair_x_v", (B * Rv, self.st[1].H)), 1)]
+            else:
+                ins = [("input_ids", self.buf("pair_ids", (B, T), i64), 0), ("token_type_ids", self.buf("pair_type_ids", (B, T), i64), 0),
+                       ("image_feat", self.buf("pair_feat", (B, Rv, cfg.v_feature_size), f32), 1),
+                       ("image_loc", self.buf("pair_loc", (B, Rv, cfg.num_locs), f32), 1)]
+            self.pair_inputs = ins + [("attention_mask", raw[0], 0), ("image_attention_mask", raw[1], 1)]
+            a = self.pair_args = self.k(L.PairGatherArgs())
+            for k, (_, t, side) in enumerate(self.pair_inputs):
+                a.dst[k], a.bytes[k], a.side[k] = t.data_ptr(), t.numel() * t.element_size() // B, side
+            a.nseg, a.npairs = len(self.pair_inputs), B
+            mask_prep(0, raw[0])
+            mask_prep(1, raw[1])
+            if per_modality:
+                self.x = [ins[0][1], ins[1][1]]
+            elif kind == "visualbert":
+                self._emb_visualbert("bert.embeddings.")
+            else:
+                self._emb_vlbert("bert.embeddings.")
+            prefix = set(text_subs) | set(vision_subs)
+            sublayers([n for n in kinds if n not in prefix])
+            self._heads_score()
+            self.bind_inputs({name: t for name, t, _ in self.pair_inputs})
+        self.fwd.freeze()
+        self.bwd.freeze()
+
+    def _heads_score(self):
+        """Poolers, fusion and the scoring head of the pair list, as the task plan computes them in eval mode (_heads_tasks: VL-logit's
+        Linear(P, 1) on the fused pooled vector) or, for task None, as BertForVLPreTraining._scores computes seq_relationship_score: the fp32
+        product (sum) of the two bf16 pooled vectors rounded to bf16 -- what vk_pool_fuse_fwd computes without dropout -- then Linear(P, 2)."""
+        cfg, B, H, T, Rv = self.cfg, self.B, self.H, self.T, self.Rv
+        f = self.fwd.ops
+        fm, P = cfg.fusion_method, cfg.pooler_size
+        if fm not in ("mul", "sum", "text"):
+            raise ValueError("fusion method %r has no ITM head to score with" % fm)
+        if (fm != "text" and P != cfg.v_pooler_size) or P % 64:
+            raise NotImplementedError("pooler sizes must match and be multiples of 64")
+        x_t, x_v = self.x
+        Hv = self.st[1].H
+        pt, pv = self.buf("pooled_t", (B, P)), None
+        pools = [self.prob(x_t, self.W("bert.t_pooler.dense.weight"), pt, B, P, H, T * H, H, P, bias=self.Pm("bert.t_pooler.dense.bias"))]
+        if fm != "text":
+            pv = self.buf("pooled_v", (B, P))
+            pools.append(self.prob(x_v, self.W("bert.v_pooler.dense.weight"), pv, B, P, Hv, Rv * Hv, Hv, P, bias=self.Pm("bert.v_pooler.dense.bias")))
+        self.gemm(f, L.NT, L.EPI_RELU, pools)
+        pooled = self.buf("pooled", (B, P))
+        fuse = {"mul": L.FUSE_MUL, "sum": L.FUSE_SUM, "text": L.FUSE_TEXT}[fm]
+        f.append((L.OP_GENERIC, 0, 0, 0, self.generic(L.FN_POOL_FWD, p=(pt, pv, pooled), n=(B, P, 0, fuse)), None, None))
+        if self.task is not None:
+            task_id, tcfg = self.task
+            if tcfg["type"] != "VL-logit":
+                raise ValueError("task type %r does not score a pair (VL-logit does)" % tcfg["type"])
+            wname, C = "clfs_dict.%s." % task_id, 1
+        else:
+            wname, C = "cls.bi_seq_relationship.", 2
+        self.score_out = self.buf("score_logits", (B, 64), torch.float32)
+        self.score_classes = C
+        self.gemm(f, L.NT, L.EPI_F32, [self.prob(pooled, self.W(wname + "weight"), self.score_out, B, C, P, P, P, 64, bias=self.Pm(wname + "bias"), n_store=64)])
+
     # -- gradient buffers of the hidden states.  dX[m] ping-pongs between two buffers: the k-th sub-layer (in
     # forward order) that transforms x[m] reads d(loss)/d(its output) from buffer k%2 and writes the gradient of
     # its input to buffer (k-1)%2; the embeddings read buffer 0, the heads fill buffer (final k)%2.
@@ -698,6 +810,8 @@ class StepEngine:
         dr = self.drop(cfg.hidden_dropout_prob)
         f.append((L.OP_LN_FWD, 0, 0, 0, self.ln_args(z, None, pre + "LayerNorm.weight", pre + "LayerNorm.bias", y, None, mean, rstd, st.M, dr, post=1), None, None))
         self.x[0] = y
+        if self.fwd_only:
+            return []
         # backward
         b = []
         dz = self.tmp("dz0", (st.M, H))
@@ -767,6 +881,8 @@ class StepEngine:
         dr = self.drop(cfg.v_hidden_dropout_prob)
         self.fwd.ops.append((L.OP_LN_FWD, 0, 0, 0, self.ln_args(proj, loc, pre + "LayerNorm.weight", pre + "LayerNorm.bias", y, proj, mean, rstd, st.M, dr, post=1, H=H), None, None))
         self.x[1] = y
+        if self.fwd_only:
+            return []
         b = []
         dz = self.tmp("dz1", (st.M, H))
         b.append((L.OP_LN_BWD, 0, 0, 0, self.ln_bwd_args(self._dx(1, 0), proj, mean, rstd, pre + "LayerNorm.weight", pre + "LayerNorm.bias", dz, None, st.M, dr, post=1, H=H), None, None))
@@ -788,6 +904,8 @@ class StepEngine:
         dr = self.drop(cfg.v_hidden_dropout_prob)
         f.append((L.OP_GENERIC, 0, 0, 0, self.generic(L.FN_ADD_DROPOUT, p=(a_n, b_n, y), n=(st.M, H, 0), f=(0.5,), drop=dr), None, None))
         self.x[1] = y
+        if self.fwd_only:
+            return []
         b = []
         g = self.tmp("dz1", (st.M, H))
         b.append((L.OP_GENERIC, 0, 0, 0, self.generic(L.FN_ADD_DROPOUT, p=(self._dx(1, 0), None, g), n=(st.M, H, 1), f=(0.5,), drop=dr), None, None))
@@ -813,6 +931,8 @@ class StepEngine:
         type1 = self.Pm(pre + "token_type_embeddings.weight")[1]
         f.append((L.OP_LN_FWD, 0, 0, 0, self.ln_args(a_n, b_n, pre + "v_LayerNorm.weight", pre + "v_LayerNorm.bias", y, z, st_a[4], st_a[5], st.M, dr, post=1, addvec=type1), None, None))
         self.x[1] = y
+        if self.fwd_only:
+            return []
         b = []
         dz = self.tmp("dz1", (st.M, H))
         b.append((L.OP_LN_BWD, 0, 0, 0, self.ln_bwd_args(self._dx(1, 0), z, st_a[4], st_a[5], pre + "v_LayerNorm.weight", pre + "v_LayerNorm.bias", dz, None, st.M, dr, post=1), None, None))
@@ -859,6 +979,8 @@ class StepEngine:
         f.append((L.OP_LN_FWD, 0, 0, 0, self.ln_args(zt, None, gn, bn, yt, None, stats[0], stats[1], st_t.M, dr, post=1, segs=seg_t), None, None))
         f.append((L.OP_LN_FWD, 0, 0, 0, self.ln_args(proj, None, gn, bn, yv, zv, stats[2], stats[3], st_v.M, dr, post=1, addvec=vec, segs=seg_v), None, None))
         self.x = [yt, yv]
+        if self.fwd_only:
+            return []
         b = []
         dzt, dzv = self.tmp("dz0", (st_t.M, H)), self.tmp("dz1", (st_v.M, H))
         b.append((L.OP_LN_BWD, 0, 0, 0, self.ln_bwd_args(self._dx(0, 0), zt, stats[0], stats[1], gn, bn, dzt, None, st_t.M, dr, post=1, segs=seg_t), None, None))
@@ -958,6 +1080,8 @@ class StepEngine:
         f.append((L.OP_LN_FWD, 0, 0, 0, self.ln_args(tz, None, gn, bn, yt, None, so[4], so[5], st_t.M, dr1, post=1, segs=seg_t), None, None))
         f.append((L.OP_LN_FWD, 0, 0, 0, self.ln_args(vz, None, gn, bn, yv, None, so[6], so[7], st_v.M, dr1, post=1, segs=seg_v), None, None))
         self.x = [yt, yv]
+        if self.fwd_only:
+            return []
         # ---- backward
         b = []
         dzt, dzv = self.tmp("dz0", (st_t.M, H)), self.tmp("dz1", (st_v.M, H))
@@ -1020,6 +1144,8 @@ class StepEngine:
         cfg, B = self.cfg, self.B
         f = self.fwd.ops
         gate = [[int(n in cfg.tt_attn_sublayers), int(n in cfg.tv_attn_sublayers)], [int(n in cfg.vt_attn_sublayers), int(n in cfg.vv_attn_sublayers)]]
+        if self.only is not None:          # a score prefix: this stream's self-attention only (before the split no block crosses the streams)
+            gate = [[g if i == j == self.only else 0 for j, g in enumerate(row)] for i, row in enumerate(gate)]
         act = [bool(gate[0][0] or gate[0][1]), bool(gate[1][0] or gate[1][1])]
         names, shared = self._names(n, "attn")
         ms = [m for m in range(2) if act[m]]
@@ -1119,6 +1245,8 @@ class StepEngine:
                                     fp8_out=self.x8[m], H=Hm[m]))
             self.x[m] = y[m]
         self._ln_pair(f, L.OP_LN_FWD, lnf)                     # both streams in one launch when their widths agree
+        if self.fwd_only:
+            return []
         # ------------- backward
         b = []
         dz, dd, dctx, dqkv, dxn, dxi = {}, {}, {}, {}, {}, {}
@@ -1182,7 +1310,7 @@ class StepEngine:
         for m in range(2):
             if Im[m] % 64:
                 raise NotImplementedError("intermediate sizes must be multiples of 64")
-        act = [n in cfg.t_ff_sublayers, n in cfg.v_ff_sublayers]
+        act = [n in cfg.t_ff_sublayers and self.only in (None, 0), n in cfg.v_ff_sublayers and self.only in (None, 1)]
         names, shared = self._names(n, "ff")
         ms = [m for m in range(2) if act[m]]
         tag = "L%d_" % n
@@ -1237,6 +1365,8 @@ class StepEngine:
                                     fp8_out=self.x8[m], H=Hm[m]))
             self.x[m] = y[m]
         self._ln_pair(f, L.OP_LN_FWD, lnf)                     # both streams in one launch when their widths agree
+        if self.fwd_only:
+            return []
         b = []
         dz, dd, du, dxn, dxi = {}, {}, {}, {}, {}
         lnb = []

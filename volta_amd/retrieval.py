@@ -1,0 +1,262 @@
+"""Image-caption retrieval scoring (the reference's eval_retrieval.py:161-222) with the modality-only layers run once per input.
+
+The driver scores every caption against every image by calling the whole model on [caption repeated 500 times, 500 images] pairs.  In a
+two-stream model the sub-layers in front of the first cross-attention depend on one modality only, and so does a per-modality embedding:
+`split_plan` finds them, `RetrievalScorer.encode_captions` / `encode_images` run them once per caption / image, and `score_matrix` /
+`score_pairs` run only the mixing suffix per pair, on inputs that one vk_pair_gather launch per pair chunk copies out of the prefix outputs
+(csrc/pairs.hip).  Every launch of these plans is a launch of the model's own forward at another batch size: eval semantics, bf16
+activations, no dropout, no backward.
+
+    scorer = RetrievalScorer(model, task_id="TASK8", pair_chunk=1000)
+    caps = scorer.encode_captions(input_ids, segment_ids, input_mask)      # [Nc, T] each, on the GPU
+    imgs = scorer.encode_images(features, spatials, image_mask)            # [Ni, R, 2048], [Ni, R, num_locs], [Ni, R]
+    S = scorer.score_matrix(caps, imgs)                                    # fp32 [Nc, Ni] on the device, no host synchronisation
+    s = scorer.score_pairs(caps, imgs, cap_idx, img_idx)                   # fp32 [P] for an explicit pair list (re-ranking)
+
+Scores: a BertForVLTasks with a VL-logit task gives its raw logit (eval_retrieval.py:191-195); a BertForVLPreTraining (zero-shot) gives
+softmax(seq_relationship_score)[:, 0] (eval_retrieval.py:181-185).  The scorer leaves the model's state alone: `training`, the dropout step
+counter, the model's last forward and its engines; it reads the current weights (the bf16 copies are refreshed as the model's forward
+refreshes them).  Handles hold prefix outputs computed with the weights of the time they were encoded.
+"""
+import ctypes as C
+
+import torch
+
+from .modules import sublayer_schedule
+
+
+def _first_mixing(config):
+    """Number of the first sub-layer in which a stream attends to the other one (len(schedule) when none does)."""
+    sched = sublayer_schedule(config)
+    mix = set(config.tv_attn_sublayers) | set(config.vt_attn_sublayers)
+    return min(mix) if mix else len(sched)
+
+
+def split_plan(config):
+    """(sub-layers that run per caption, sub-layers that run per image, whether each embedding is per modality).
+
+    The first sub-layer in tv_attn_sublayers | vt_attn_sublayers ends both prefixes: before it, an attention sub-layer in
+    tt_attn_sublayers and a feed-forward sub-layer in t_ff_sublayers transform the text stream from text alone, vv_attn_sublayers and
+    v_ff_sublayers the vision stream from vision alone.  VisualBERT's and VL-BERT's embeddings mix the modalities (one LayerNorm over
+    [text | vision], VL-BERT's text tokens carry a region's feature), so those models have no per-modality stage at all."""
+    if config.image_embeddings not in ("vilbert", "lxmert", "uniter"):
+        return [], [], False
+    first = _first_mixing(config)
+    text, vision = [], []
+    for n, typ in sublayer_schedule(config):
+        if n >= first:
+            break
+        if n in (config.tt_attn_sublayers if typ == "attn" else config.t_ff_sublayers):
+            text.append(n)
+        if n in (config.vv_attn_sublayers if typ == "attn" else config.v_ff_sublayers):
+            vision.append(n)
+    return text, vision, True
+
+
+class Items:
+    """Encoded captions (side 0) or images (side 1): the per-item inputs of the pair suffix, by the names of its `pair_inputs`."""
+
+    def __init__(self, scorer, side, n, length, tensors):
+        self.scorer, self.side, self.n, self.length, self.tensors = scorer, side, n, length, tensors
+
+    def __len__(self):
+        return self.n
+
+
+class RetrievalScorer:
+    def __init__(self, model, task_id=None, pair_chunk=1000):
+        from .modeling import BertForVLPreTraining, BertForVLTasks
+        if isinstance(model, BertForVLTasks):
+            if task_id not in model.task_cfg or task_id not in model.clfs_dict:
+                raise ValueError("unknown task id %r" % (task_id,))
+            if model.task_cfg[task_id]["type"] != "VL-logit":
+                raise ValueError("task %r is of type %r; retrieval scores a VL-logit task (eval_retrieval.py:191)" % (task_id, model.task_cfg[task_id]["type"]))
+            self.task = (task_id, model.task_cfg[task_id])
+        elif isinstance(model, BertForVLPreTraining):
+            if task_id is not None:
+                raise ValueError("the zero-shot scorer (BertForVLPreTraining) takes no task id")
+            self.task = None
+        else:
+            raise ValueError("scores come from a BertForVLTasks with a VL-logit task or a BertForVLPreTraining, not from %s" % type(model).__name__)
+        cfg = model.config
+        if cfg.fusion_method not in ("mul", "sum", "text"):
+            raise ValueError("fusion method %r has no ITM head (encoders.py:744-747, 1192-1193)" % cfg.fusion_method)
+        if model.__dict__.get("_fp8", False):
+            raise NotImplementedError("the retrieval scorer runs the bf16 projections; set_projection_dtype('bf16') first")
+        if int(pair_chunk) < 1:
+            raise ValueError("pair_chunk must be positive, got %r" % (pair_chunk,))
+        self.device = next(model.parameters()).device
+        if self.device.type != "cuda":
+            raise ValueError("the model is not on the GPU (model.cuda())")
+        self.model, self.cfg, self.pair_chunk = model, cfg, int(pair_chunk)
+        self.split = split_plan(cfg)
+        # VL-BERT's text position ids depend on the batch: past the SHORTEST caption of the batch every text position is shifted by the
+        # region count (vk_vlbert_positions, the reference's expanded-view quirk, volta/embeddings.py).  The driver's batches hold one
+        # caption, so the scorer's pair chunks do as well, and a pair's score is the one the driver computes.
+        self.one_caption_per_chunk = cfg.image_embeddings == "vl-bert"
+        self._arena, self._engines = None, {}
+
+    # ------------------------------------------------------------------ plumbing
+    def _prepare(self):
+        """The model's arena with current bf16 weights; the scorer's plans are rebuilt when the arena was."""
+        if self.model.__dict__.get("_fp8", False):
+            raise NotImplementedError("the retrieval scorer runs the bf16 projections; set_projection_dtype('bf16') first")
+        arena = self.model.materialize()
+        if arena is not self._arena:
+            self._arena, self._engines = arena, {}
+        arena.sync_optimizer()           # a pipelined optimizer step still in flight: every plan here reads all of the weights
+        arena.refresh_shadow()
+        return arena
+
+    def _engine(self, part, B, T, Rv):
+        from .engine import StepEngine
+        key = (part, B, T, Rv)
+        eng = self._engines.get(key)
+        if eng is None:
+            eng = StepEngine(self.cfg, self._arena, B, T, Rv, False, heads="score", task=self.task if part == "pair" else None, part=part, split=self.split)
+            self._engines[key] = eng
+        return eng
+
+    def _tensor(self, x, dtype, shape, what):
+        if not isinstance(x, torch.Tensor):
+            raise ValueError("%s must be a tensor" % what)
+        if x.device != self.device:
+            raise ValueError("%s is on %s, the model on %s" % (what, x.device, self.device))
+        if tuple(x.shape) != tuple(shape):
+            raise ValueError("%s has shape %s, expected %s" % (what, tuple(x.shape), tuple(shape)))
+        return x.to(dtype).contiguous()
+
+    # ------------------------------------------------------------------ prefixes
+    def encode_captions(self, input_ids, segment_ids=None, input_mask=None):
+        if not isinstance(input_ids, torch.Tensor) or input_ids.dim() != 2 or input_ids.shape[0] < 1 or input_ids.shape[1] < 1:
+            raise ValueError("input_ids must be a non-empty [Nc, T] tensor")
+        Nc, T = input_ids.shape
+        ids = self._tensor(input_ids, torch.int64, (Nc, T), "input_ids")
+        tt = self._tensor(segment_ids, torch.int64, (Nc, T), "segment_ids") if segment_ids is not None else torch.zeros_like(ids)
+        mask = self._tensor(input_mask, torch.int64, (Nc, T), "input_mask") if input_mask is not None else torch.ones_like(ids)
+        tensors = dict(input_ids=ids, token_type_ids=tt, attention_mask=mask)
+        if self.split[2]:
+            self._prepare()
+            H = self.cfg.hidden_size
+            x = torch.empty(Nc * T, H, dtype=torch.bfloat16, device=self.device)
+            for c0 in range(0, Nc, self.pair_chunk):
+                nb = min(self.pair_chunk, Nc - c0)
+                eng = self._engine("text", nb, T, 1)
+                eng.bind_inputs({k: v[c0:c0 + nb] for k, v in tensors.items()})
+                eng.fwd.run()
+                x[c0 * T:(c0 + nb) * T].copy_(eng.score_out)
+            tensors["x_t"] = x
+        return Items(self, 0, Nc, T, tensors)
+
+    def encode_images(self, features, spatials, image_mask=None):
+        if not isinstance(features, torch.Tensor) or features.dim() != 3 or features.shape[0] < 1 or features.shape[1] < 1:
+            raise ValueError("features must be a non-empty [Ni, R, v_feature_size] tensor")
+        Ni, Rv = features.shape[:2]
+        feat = self._tensor(features, torch.float32, (Ni, Rv, self.cfg.v_feature_size), "features")
+        loc = self._tensor(spatials, torch.float32, (Ni, Rv, self.cfg.num_locs), "spatials")
+        mask = self._tensor(image_mask, torch.int64, (Ni, Rv), "image_mask") if image_mask is not None else torch.ones(Ni, Rv, dtype=torch.int64, device=self.device)
+        tensors = dict(image_feat=feat, image_loc=loc, image_attention_mask=mask)
+        if self.split[2]:
+            self._prepare()
+            Hv = self.cfg.v_hidden_size
+            x = torch.empty(Ni * Rv, Hv, dtype=torch.bfloat16, device=self.device)
+            for i0 in range(0, Ni, self.pair_chunk):
+                nb = min(self.pair_chunk, Ni - i0)
+                eng = self._engine("image", nb, 1, Rv)
+                eng.bind_inputs({k: v[i0:i0 + nb] for k, v in tensors.items()})
+                eng.fwd.run()
+                x[i0 * Rv:(i0 + nb) * Rv].copy_(eng.score_out)
+            tensors["x_v"] = x
+        return Items(self, 1, Ni, Rv, tensors)
+
+    # ------------------------------------------------------------------ pairs
+    def _check_items(self, caps, imgs):
+        if not (isinstance(caps, Items) and caps.side == 0 and caps.scorer is self):
+            raise ValueError("caps must come from this scorer's encode_captions")
+        if not (isinstance(imgs, Items) and imgs.side == 1 and imgs.scorer is self):
+            raise ValueError("imgs must come from this scorer's encode_images")
+        if caps.length + imgs.length > 512:
+            raise ValueError("%d text + %d region rows: more than 512 keys per query row" % (caps.length, imgs.length))
+
+    def _run_pairs(self, caps, imgs, npairs, cross=None, idx=None):
+        """One pair chunk: gather, then the suffix list.  -> fp32 logits [npairs, classes] (a view of the plan's output buffer)."""
+        eng = self._engine("pair", npairs, caps.length, imgs.length)
+        a = eng.pair_args
+        for k, (name, _, side) in enumerate(eng.pair_inputs):
+            a.src[k] = (caps if side == 0 else imgs).tensors[name].data_ptr()
+        a.n_items[0], a.n_items[1] = caps.n, imgs.n
+        if cross is not None:
+            a.cap_idx = a.img_idx = None
+            a.c0, a.nc, a.i0, a.ni = cross
+        else:
+            a.cap_idx, a.img_idx = idx[0].data_ptr(), idx[1].data_ptr()
+            a.c0 = a.nc = a.i0 = a.ni = 0
+        from . import _lib as L
+        L.check(L.lib.vk_pair_gather(C.byref(a), L.stream_ptr()))
+        eng.fwd.run()
+        return eng.score_out[:npairs, :eng.score_classes]
+
+    def _scores(self, logits):
+        """fp32 scores of [n, classes] logits: the VL-logit itself, or the zero-shot match probability softmax(itm)[:, 0]."""
+        return logits[:, 0] if self.task is not None else torch.softmax(logits, dim=1)[:, 0]
+
+    def score_matrix(self, caps, imgs, return_logits=False):
+        """fp32 [Nc, Ni] scores of every caption against every image, left on the device (no host synchronisation).  Pair chunks of at most
+        pair_chunk pairs: one caption against image blocks of pair_chunk, or as many whole captions as fit against all images (one caption
+        per chunk for VL-BERT, whose text positions depend on the batch's shortest caption).
+        return_logits: also the raw logits, fp32 [Nc, Ni, classes] (1 for VL-logit, the two ITM logits for zero-shot)."""
+        self._check_items(caps, imgs)
+        self._prepare()
+        Nc, Ni, P = caps.n, imgs.n, self.pair_chunk
+        C_ = 1 if self.task is not None else 2
+        S = torch.empty(Nc, Ni, dtype=torch.float32, device=self.device)
+        Lg = torch.empty(Nc, Ni, C_, dtype=torch.float32, device=self.device) if return_logits else None
+        if Ni >= P or self.one_caption_per_chunk:
+            blocks = [(c, 1, i0, min(P, Ni - i0)) for c in range(Nc) for i0 in range(0, Ni, P)]
+        else:
+            per = P // Ni
+            blocks = [(c0, min(per, Nc - c0), 0, Ni) for c0 in range(0, Nc, per)]
+        with torch.no_grad():
+            for c0, nc, i0, ni in blocks:
+                lg = self._run_pairs(caps, imgs, nc * ni, cross=(c0, nc, i0, ni))
+                S[c0:c0 + nc, i0:i0 + ni].copy_(self._scores(lg).view(nc, ni))
+                if Lg is not None:
+                    Lg[c0:c0 + nc, i0:i0 + ni].copy_(lg.view(nc, ni, C_))
+        return (S, Lg) if return_logits else S
+
+    def score_pairs(self, caps, imgs, cap_idx, img_idx, return_logits=False):
+        """fp32 [P] scores of the pairs (cap_idx[p], img_idx[p]) (integer tensors of one length on the model's device; re-ranking).  The
+        indices are range-checked on the host (one synchronisation)."""
+        self._check_items(caps, imgs)
+        ci = self._tensor(cap_idx, torch.int64, tuple(cap_idx.shape), "cap_idx") if isinstance(cap_idx, torch.Tensor) else None
+        ii = self._tensor(img_idx, torch.int64, tuple(img_idx.shape), "img_idx") if isinstance(img_idx, torch.Tensor) else None
+        if ci is None or ii is None or ci.dim() != 1 or ci.shape != ii.shape:
+            raise ValueError("cap_idx and img_idx must be 1-D integer tensors of one length")
+        n = ci.numel()
+        if n and not (0 <= int(ci.min()) and int(ci.max()) < caps.n and 0 <= int(ii.min()) and int(ii.max()) < imgs.n):
+            raise ValueError("pair indices out of range (%d captions, %d images)" % (caps.n, imgs.n))
+        self._prepare()
+        C_ = 1 if self.task is not None else 2
+        s = torch.empty(n, dtype=torch.float32, device=self.device)
+        Lg = torch.empty(n, C_, dtype=torch.float32, device=self.device) if return_logits else None
+        if self.one_caption_per_chunk:        # chunks of one caption each: the pairs grouped by caption (their order kept within a group)
+            order = torch.sort(ci, stable=True)[1]
+            counts = torch.bincount(ci, minlength=caps.n).tolist()
+            groups, start = [], 0
+            for cnt in counts:
+                groups += [(start + q, min(self.pair_chunk, cnt - q)) for q in range(0, cnt, self.pair_chunk)]
+                start += cnt
+            ci, ii = ci[order], ii[order]
+        else:
+            order = None
+            groups = [(p0, min(self.pair_chunk, n - p0)) for p0 in range(0, n, self.pair_chunk)]
+        with torch.no_grad():
+            for p0, m in groups:
+                lg = self._run_pairs(caps, imgs, m, idx=(ci[p0:p0 + m], ii[p0:p0 + m]))
+                s[p0:p0 + m].copy_(self._scores(lg))
+                if Lg is not None:
+                    Lg[p0:p0 + m].copy_(lg)
+            if order is not None:            # back to the caller's order
+                s = torch.empty_like(s).index_copy_(0, order, s)
+                Lg = torch.empty_like(Lg).index_copy_(0, order, Lg) if Lg is not None else None
+        return (s, Lg) if return_logits else s
