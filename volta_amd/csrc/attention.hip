@@ -520,13 +520,14 @@ static int fill(AttnK& k, const vk_attn_args* a, const vk_attn_bwd_args* bw) {
         const bool qa = a->gate[m][0] || a->gate[m][1], ka = a->gate[0][m] || a->gate[1][m];
         if (!qa && !ka) continue;
         if (a->L[m] <= 0) return set_error("vk_gated_attn: modality %d is gated on but has length %d", m, a->L[m]);
+        // only modalities that are on count against the tiles, as in attn_mfma_ok: a gated-off modality's length is not read
+        if (a->L[m] > (m == 0 ? 64 : 128)) return set_error("vk_gated_attn: lengths (%d, %d) exceed the (64, 128) tile budget", a->L[0], a->L[1]);
         if ((a->ld[m] & 7) || (a->ldo[m] & 7)) return set_error("vk_gated_attn: row strides must be multiples of 8");
         if (ka && (!a->k[m] || !a->v[m] || !a->mask[m])) return set_error("vk_gated_attn: K/V/mask of modality %d missing", m);
         if (qa && (!a->q[m] || !a->ctx[m] || !a->lse[m])) return set_error("vk_gated_attn: Q/ctx/lse of modality %d missing", m);
         if (bw && qa && (!bw->dctx[m] || !bw->dq[m])) return set_error("vk_gated_attn_bwd: dctx/dq of modality %d missing", m);
         if (bw && ka && (!bw->dk[m] || !bw->dv[m])) return set_error("vk_gated_attn_bwd: dk/dv of modality %d missing", m);
     }
-    if (a->L[0] > 64 || a->L[1] > 128) return set_error("vk_gated_attn: lengths (%d, %d) exceed the (64, 128) tile budget", a->L[0], a->L[1]);
     return 0;
 }
 
