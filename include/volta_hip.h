@@ -451,6 +451,39 @@ int vk_vis_loss_bwd(const vk_vis_loss_args* a, void* dlogits, int ldd, const flo
    out[(b*R + r) * 127 + j]; j < 89: a region of another image, j >= 89: another region of the same image.  B, R >= 2. */
 int vk_nce_negatives(vk_dropout rng, int B, int R, int32_t* out, vk_stream_t s);
 
+/* ------------------------------------------------------------------------------------------------
+ * Losses and scores of the fine-tuning step (volta_amd/csrc/taskloss.hip) replace what ForwardModelsTrain / ForwardModelsVal compute in
+ * torch behind the model (volta/task_utils.py:24-27 criteria, :140-281 the per-type loss and score, :429-434 compute_score_with_logits).
+ * The logits are read in place in the engine's fp32 `task_logits` buffer [rows, ld] (ld = C rounded up to 64; the pad columns are never
+ * read).  A "group" is what the reference takes torch.max over; element (g, j), j < n:
+ *   VK_TASK_BCE_SCALED   VL-classifier, VL-classifier-GQA (:238-246)  logits[g * ld + j], target fp32 [groups, n];
+ *                        loss = sum of BCE-with-logits / groups (= mean * n), score = sum_g target[g, argmax_j]
+ *   VK_TASK_BCE_MEAN     VL-binary-classifier, VL-tri-classifier (:271-279)  same with loss = sum / (groups * n)
+ *   VK_TASK_BCE_REGIONS  V-logit (:254-259, encoders.py:1198-1199)  logits[(g * n + j) * ld] + (1 - mask[g * n + j]) * -10000,
+ *                        target fp32 [groups, n], mask int64 [groups, n] or NULL; loss = sum / groups (= mean * n),
+ *                        score = #groups whose arg-max region has target > 0.5
+ *   VK_TASK_CE_OPTIONS   VL-logit (:248-252)  logits[(g * n + j) * ld], target int64 [groups] (clamped to [0, n));
+ *                        loss = mean_g (logsumexp_j - x[target]), score = #groups with argmax == target
+ * The arg-max is the FIRST index of the maximum.  vk_task_loss_fwd writes out[0] = loss, out[1] = score sum, row_argmax[g]; the per-group
+ * terms go through `work` (vk_task_loss_work_bytes(groups) bytes: double loss[groups], then float score[groups]) and are summed in a fixed order by a second one-workgroup launch: the
+ * same bits on every run, no floating-point atomics.  vk_task_loss_bwd writes dlogits (bf16 [rows, ld], every pad column zero)
+ * = *gscale x d loss / d logits, computed in fp32 from the same logits and target and rounded once (to nearest even); gscale is a DEVICE
+ * scalar (the incoming gradient of the loss).
+ * ---------------------------------------------------------------------------------------------- */
+enum { VK_TASK_BCE_SCALED = 0, VK_TASK_BCE_MEAN = 1, VK_TASK_BCE_REGIONS = 2, VK_TASK_CE_OPTIONS = 3 };
+typedef struct vk_task_loss_args {
+    const float* logits;       /* fp32 [rows, ld]: rows = groups (BCE_SCALED / BCE_MEAN), groups * n (BCE_REGIONS / CE_OPTIONS) */
+    const void* target;        /* fp32 [groups, n], or int64 [groups] for VK_TASK_CE_OPTIONS */
+    const int64_t* mask;       /* VK_TASK_BCE_REGIONS: image_attention_mask [groups, n] (1 = region present) or NULL */
+    void* work;                /* vk_task_loss_work_bytes(groups) bytes (forward only) */
+    float* out;                /* forward: float[2] = (loss, score sum) */
+    int32_t* row_argmax;       /* forward: [groups] */
+    int32_t kind, groups, n, ld;
+} vk_task_loss_args;
+int64_t vk_task_loss_work_bytes(int groups);
+int vk_task_loss_fwd(const vk_task_loss_args* a, vk_stream_t s);
+int vk_task_loss_bwd(const vk_task_loss_args* a, const float* gscale, void* dlogits, vk_stream_t s);
+
 /* additive attention mask (1 - m) * -10000 (encoders.py:983-991) */
 int vk_mask_prep(const int64_t* mask, float* out, int n, vk_stream_t s);
 

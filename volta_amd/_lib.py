@@ -115,6 +115,14 @@ class VisLossArgs(C.Structure):
 
 
 VIS_MSE, VIS_NCE, VIS_XENT, VIS_HUBER = 1, 2, 3, 5
+
+
+class TaskLossArgs(C.Structure):
+    _fields_ = [("logits", c_p), ("target", c_p), ("mask", c_p), ("work", c_p), ("out", c_p), ("row_argmax", c_p),
+                ("kind", i32), ("groups", i32), ("n", i32), ("ld", i32)]
+
+
+TASK_BCE_SCALED, TASK_BCE_MEAN, TASK_BCE_REGIONS, TASK_CE_OPTIONS = range(4)
 NCE_ACROSS, NCE_INSIDE, NCE_MAX_SAMPLES = 89, 38, 128
 FUSE_MUL, FUSE_SUM, FUSE_TEXT = 0, 1, 2
 
@@ -261,6 +269,9 @@ _sig("vk_b64_decode", C.c_int, C.c_char_p, C.c_size_t, c_p, C.c_size_t, C.POINTE
 _sig("vk_vlbert_positions", C.c_int, c_p, C.c_int, C.c_int, C.c_int, c_p, c_p, c_p)
 _sig("vk_vis_loss_fwd", C.c_int, C.POINTER(VisLossArgs), c_p)
 _sig("vk_vis_loss_bwd", C.c_int, C.POINTER(VisLossArgs), c_p, C.c_int, c_p, c_p)
+_sig("vk_task_loss_work_bytes", C.c_int64, C.c_int)
+_sig("vk_task_loss_fwd", C.c_int, C.POINTER(TaskLossArgs), c_p)
+_sig("vk_task_loss_bwd", C.c_int, C.POINTER(TaskLossArgs), c_p, c_p, c_p)
 _sig("vk_nce_negatives", C.c_int, Dropout, C.c_int, C.c_int, c_p, c_p)
 _sig("vk_pool_mul_bwd", C.c_int, c_p, C.c_int, c_p, c_p, c_p, c_p, C.c_int, C.c_int, Dropout, c_p)
 _sig("vk_mask_prep", C.c_int, c_p, c_p, C.c_int, c_p)
@@ -308,7 +319,7 @@ EXPORTS = ["vk_version", "vk_device_arch", "vk_last_error", "vk_set_seed", "vk_c
            "vk_add_dropout", "vk_colsum_bf16", "vk_vlbert_prep_fwd", "vk_vlbert_maskgrad", "vk_rowgroup_sum_bf16",
            "vk_relu_bwd_bf16", "vk_copy_async", "vk_select_rows", "vk_gather_rows", "vk_scatter_rows_add", "vk_xent_fwd",
            "vk_xent_bwd", "vk_kl_fwd", "vk_kl_bwd", "vk_loss_finalize", "vk_pool_mul_fwd", "vk_pool_mul_bwd",
-           "vk_pool_fuse_fwd", "vk_pool_fuse_bwd", "vk_text_end_rows", "vk_vlbert_obj_ids", "vk_vlbert_positions", "vk_vis_loss_fwd", "vk_vis_loss_bwd", "vk_nce_negatives",
+           "vk_pool_fuse_fwd", "vk_pool_fuse_bwd", "vk_text_end_rows", "vk_vlbert_obj_ids", "vk_vlbert_positions", "vk_vis_loss_fwd", "vk_vis_loss_bwd", "vk_nce_negatives", "vk_task_loss_work_bytes", "vk_task_loss_fwd", "vk_task_loss_bwd",
            "vk_mask_prep", "vk_mul_bf16", "vk_grad_norm_workspace_floats", "vk_grad_norm_clip", "vk_grad_norm_clip_masked", "vk_grad_sqnorm_chunks", "vk_grad_norm_from_chunks", "vk_adamw_step", "vk_adamw_step_on", "vk_adamw_step_list", "vk_grad_sqnorm_list", "vk_grad_sqnorm_list_work_floats", "vk_grad_seed", "vk_pair_gather", "vk_radam_step", "vk_radam_step_list",
            "vk_axpy_f32", "vk_sum_slabs_f32", "vk_sum_slabs_bf16", "vk_memset_async", "vk_hold_cus", "vk_gate_wait", "vk_bump_u64", "vk_store_u64", "vk_gate_value", "vk_comm_standin", "vk_gemm_reserve_cus", "vk_side_tail", "vk_run_ops", "vk_run_ops_timed", "vk_side_join", "vk_side_join_from", "vk_side_stream", "vk_side_enable", "vk_concap_batch",
            "vk_lmdb_open", "vk_lmdb_close", "vk_lmdb_entries", "vk_lmdb_first", "vk_lmdb_next", "vk_lmdb_get", "vk_concap_record_decode", "vk_concap_records_decode", "vk_b64_decode",

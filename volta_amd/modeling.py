@@ -725,6 +725,71 @@ class _TaskStep(torch.autograd.Function):
         return None, None, None
 
 
+_TASK_LOSS_KINDS = {"bce_scaled": 0, "bce_mean": 1, "bce_regions": 2, "ce_options": 3}      # VK_TASK_* of include/volta_hip.h
+
+
+def _task_loss_args(eng, tensors, target, kind, num_options):
+    """vk_task_loss_args over the engine's logits for this step's target; the result buffers live with the engine plan."""
+    from . import _lib as L
+    code = _TASK_LOSS_KINDS[kind]
+    shape, ld = eng.pred_shape, eng.pred.shape[1]
+    mask = None
+    if kind == "bce_regions":
+        if len(shape) != 3:
+            raise ValueError("kind 'bce_regions' needs a region-logit task (V-logit); this task predicts %r" % (shape,))
+        groups, n = shape[0], shape[1]
+        mask = tensors["image_attention_mask"]
+    elif len(shape) != 2:
+        raise ValueError("kind %r needs a pooled-output task; this task predicts %r" % (kind, shape))
+    elif kind == "ce_options":
+        if shape[1] != 1 or not num_options or shape[0] % int(num_options):
+            raise ValueError("kind 'ce_options' needs a one-score task (VL-logit) and num_options dividing its %d rows" % shape[0])
+        groups, n = shape[0] // int(num_options), int(num_options)
+    else:
+        groups, n = shape
+    if kind == "ce_options":
+        if target.dtype != torch.int64 or target.numel() != groups:
+            raise ValueError("kind 'ce_options' takes an int64 target of %d option indices" % groups)
+    elif target.dtype != torch.float32 or target.numel() != groups * n:
+        raise ValueError("kind %r takes a float32 target of %d x %d scores, got %s %r" % (kind, groups, n, target.dtype, tuple(target.shape)))
+    bufs = eng.__dict__.get("task_loss_bufs")
+    if bufs is None or bufs[2].numel() != groups:
+        dev = eng.pred.device
+        bufs = eng.__dict__["task_loss_bufs"] = (torch.empty(L.lib.vk_task_loss_work_bytes(groups), dtype=torch.uint8, device=dev),
+                                                 torch.empty(2, dtype=torch.float32, device=dev), torch.empty(groups, dtype=torch.int32, device=dev))
+    work, out, amax = bufs
+    return L.TaskLossArgs(L.ptr(eng.pred), L.ptr(target), L.ptr(mask), L.ptr(work), L.ptr(out), L.ptr(amax), code, groups, n, ld), out, amax
+
+
+class _TaskLossStep(torch.autograd.Function):
+    """_TaskStep with the task's loss inside the node: the forward list, then vk_task_loss_fwd on the logits where the engine left them;
+    backward writes d(loss)/d(logits) x the incoming gradient (read on the device) as bf16 into the engine's seed buffer and runs the
+    backward list.  Returns (float[2] = loss, score sum; int32 arg-max per group); only the loss carries a gradient."""
+
+    @staticmethod
+    def forward(ctx, model, anchor, tensors, target, kind, num_options):
+        from . import _lib as L
+        model._engine_forward(tensors)
+        eng = model._last[0]
+        args, out, amax = _task_loss_args(eng, tensors, target, kind, num_options)
+        L.check(L.lib.vk_task_loss_fwd(args, L.stream_ptr()))
+        ctx.model, ctx.args, ctx.target = model, args, target       # the target stays alive until the backward has read it
+        res, idx = out.clone(), amax.clone()
+        ctx.mark_non_differentiable(idx)
+        return res, idx
+
+    @staticmethod
+    def backward(ctx, g_res, _g_idx):
+        from . import _lib as L
+        model = ctx.model
+        eng, _ = model._last
+        state = model._backward_begin(eng)
+        g = g_res.to(torch.float32).contiguous()                    # g[0] = d(objective)/d(loss); the score carries none
+        L.check(L.lib.vk_task_loss_bwd(ctx.args, L.ptr(g), L.ptr(eng.d_pred), L.stream_ptr()))
+        model._backward_run(eng, state)
+        return None, None, None, None, None, None
+
+
 class BertForVLTasks(PreTrainedModel):
     """Fine-tuning / evaluation model of the downstream tasks (volta/encoders.py:1117-1206): encoder, poolers, fusion + dropout and the
     task's classifier all run on the HIP engine, forward and backward; `clfs_dict` holds the classifiers' parameters under the reference's
@@ -815,6 +880,46 @@ class BertForVLTasks(PreTrainedModel):
         else:
             seq_t, seq_v = eng.taps["seq_t"].view(B, T, H).float(), eng.taps["seq_v"].view(B, Rv, Hv).float()
         return seq_t, seq_v, None if pt is None else pt.float(), None if pv is None else pv.float(), attn_maps
+
+    def task_loss(self, input_txt, input_imgs, image_loc, task_id, token_type_ids=None, attention_mask=None, image_attention_mask=None,
+                  target=None, *, kind, num_options=None):
+        """The model and the task's loss in one step (what ForwardModelsTrain / ForwardModelsVal compute behind `forward`,
+        volta/task_utils.py:140-281): returns (loss, score_sum, row_argmax) -- 0-dim fp32 device tensors and an int32 vector with the
+        arg-max of every group.  The logits never leave the engine; `loss` is differentiable with respect to every trainable parameter.
+        kind: "bce_scaled" (BCE-with-logits mean x C: VL-classifier, VL-classifier-GQA), "bce_mean" (plain mean: VL-binary-classifier,
+        VL-tri-classifier), "bce_regions" (V-logit: BCE over the masked region scores x regions) or "ce_options" (VL-logit: cross-entropy
+        over `num_options` consecutive samples, int64 target)."""
+        res, idx = self._task_loss(input_txt, input_imgs, image_loc, task_id, token_type_ids, attention_mask, image_attention_mask, target, kind, num_options)
+        return res[0], res[1].detach(), idx
+
+    def _task_loss(self, input_txt, input_imgs, image_loc, task_id, token_type_ids, attention_mask, image_attention_mask, target, kind, num_options):
+        """task_loss with loss and score still in one float[2] tensor (ForwardModelsVal reads both with one transfer)"""
+        if task_id not in self.task_cfg or task_id not in self.clfs_dict:
+            raise KeyError("unknown task id %r" % (task_id,))
+        if kind not in _TASK_LOSS_KINDS:
+            raise ValueError("kind %r (%s)" % (kind, " | ".join(_TASK_LOSS_KINDS)))
+        if target is None:
+            raise ValueError("task_loss needs the target")
+        tensors, B, T, Rv = self._prep_inputs(input_txt, input_imgs, image_loc, token_type_ids, attention_mask, image_attention_mask,
+                                              None, None, None, None)
+        dev = tensors["input_ids"].device
+        target = target.to(device=dev).contiguous()
+        self.__dict__["_cur_task"] = task_id
+        try:
+            self.materialize()
+            if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+                anchor = next(p for p in self.parameters() if p.requires_grad)
+                res, idx = _TaskLossStep.apply(self, anchor, tensors, target, kind, num_options)
+            else:
+                from . import _lib as L
+                with torch.no_grad():
+                    self._engine_forward(tensors)
+                    args, out, amax = _task_loss_args(self._last[0], tensors, target, kind, num_options)
+                    L.check(L.lib.vk_task_loss_fwd(args, L.stream_ptr()))
+                    res, idx = out.clone(), amax.clone()
+        finally:
+            self.__dict__["_cur_task"] = None
+        return res, idx
 
     def forward(self, input_txt, input_imgs, image_loc, task_id, token_type_ids=None, attention_mask=None,
                 image_attention_mask=None, output_all_encoded_layers=False, output_all_attention_masks=False):
