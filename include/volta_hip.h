@@ -740,6 +740,46 @@ typedef struct vk_concap_args {
 int vk_concap_batch(const vk_concap_args* a, vk_stream_t s);
 
 /* ------------------------------------------------------------------------------------------------
+ * Batch assembler of the fine-tuning loader (csrc/taskbatch.hip; volta_amd/datasets.py TaskLoader): what the reference's task datasets build per
+ * sample in Python (vqa_dataset.py:241-282, nlvr2_dataset.py:184-223, retrieval_dataset.py:157-254, refer_expression_dataset.py:222-269),
+ * for a whole batch from the staged images on the device.  Image slot s holds n[s] regions (features [n, F], pixel boxes [n, 4]) of an image
+ * of wh[s] = (width, height).  Its LOGICAL row list is the regions with the global row (mean feature, whole-image box) placed first
+ * (add_global = 1), last (2) or absent (0).  Output block o is described by VK_TASK_MAX_SEGS segments {slot, src_from, dst_from, count}:
+ * logical rows [src_from, src_from + count) of `slot` go to rows [dst_from, ...) of the block, cut at the end of the row list and of the
+ * block; where two segments overlap the later one wins; count <= 0 = unused.  Rows no segment reaches are zero.  Every element of every
+ * output is written (no memset needed); segment contents are bounds-checked on the device.
+ *   features   [N, R, F] fp32        spatials [N, R, num_locs] fp32: x / w, y / h (, box area / (w * h)); global row 0, 0, 1, 1 (, 1)
+ *   image_mask [N, R] int64          1 for rows < mask_count[o]
+ *   target     VK_TASK_TARGET_SCATTER: [B, num_labels] fp32, target[b][labels[p]] = scores[p] for p in [csr[b], csr[b + 1]) (labels of one
+ *              sample distinct), zero elsewhere;  VK_TASK_TARGET_IOU: [N, R] fp32, IoU (+1 pixel convention) of the row's ORIGINAL pixel box
+ *              (global row: 0, 0, w, h) with ref_box[o], zero for rows no segment reaches
+ * `mean` [S, F] fp32 is workspace for the global rows (needed when add_global != 0): rows summed in order in fp32, divided by n. */
+#define VK_TASK_MAX_SEGS 2
+#define VK_TASK_ROWS 4               /* rows of a block per workgroup */
+#define VK_TASK_TARGET_NONE 0
+#define VK_TASK_TARGET_SCATTER 1
+#define VK_TASK_TARGET_IOU 2
+typedef struct vk_task_batch_args {
+    const float* feat;               /* [S, Rcap, F] */
+    const float* boxes;              /* [S, Rcap, 4] pixels */
+    const int32_t* n;                /* [S] */
+    const int32_t* wh;               /* [S, 2] */
+    float* mean;                     /* [S, F] workspace */
+    const int32_t* segs;             /* [N, VK_TASK_MAX_SEGS, 4] */
+    const int32_t* mask_count;       /* [N] */
+    float* features;
+    float* spatials;
+    int64_t* image_mask;
+    float* target;
+    const int32_t* csr;              /* [B + 1] */
+    const int32_t* labels;
+    const float* scores;
+    const float* ref_box;            /* [N, 4] pixels */
+    int32_t S, Rcap, F, N, R, B, num_locs, add_global, target_kind, num_labels;
+} vk_task_batch_args;
+int vk_task_batch(const vk_task_batch_args* a, vk_stream_t s);
+
+/* ------------------------------------------------------------------------------------------------
  * Record readers in front of the batch producer.  Host code (no stream argument): files are memory-mapped and fields
  * are decoded straight into the caller's staging slot -- use pinned memory and one cudaMemcpyAsync per batch.
  *
@@ -800,6 +840,22 @@ int vk_wordpiece_encode_batch(const vk_wordpiece* t, const char* const* texts, c
  * columns of the extraction TSV (data/conceptual_captions/preprocess_cc_train.py:66-68) and of the task feature stores
  * (_image_features_reader.py:87-88). */
 int vk_b64_decode(const char* src, size_t n, void* dst, size_t cap, size_t* out_len);
+
+/* The base64 `features` / `boxes` fields of n task-feature records (_image_features_reader.py:87-88) decoded straight into their slots of the
+ * pinned staging arrays vk_task_batch reads, on `threads` host threads (at most 16) in ONE call.  The caller has found the fields (Python
+ * unpickles the record; the text is not copied) and sized the slots: `rows` is the region count it derived from the text length, and a
+ * payload that does not decode to exactly rows * F floats / rows * 4 floats is an error.  -1 with the first failing image's message;
+ * *failed (optional) = its index. */
+typedef struct vk_task_image {
+    const char* feat_b64;
+    size_t feat_len;
+    const char* boxes_b64;
+    size_t boxes_len;
+    float* feat;                     /* [rows, F] slot */
+    float* boxes;                    /* [rows, 4] slot */
+    int32_t rows, F;
+} vk_task_image;
+int vk_task_images_stage(const vk_task_image* jobs, int n, int threads, int* failed);
 
 #ifdef __cplusplus
 }

@@ -162,6 +162,21 @@ class PairGatherArgs(C.Structure):
                 ("i0", i32), ("ni", i32)]
 
 
+TASK_MAX_SEGS, TASK_ROWS = 2, 4      # VK_TASK_MAX_SEGS, VK_TASK_ROWS
+TASK_TARGET_NONE, TASK_TARGET_SCATTER, TASK_TARGET_IOU = range(3)
+
+
+class TaskBatchArgs(C.Structure):
+    _fields_ = [(n, c_p) for n in ("feat", "boxes", "n", "wh", "mean", "segs", "mask_count", "features", "spatials", "image_mask", "target", "csr",
+                                   "labels", "scores", "ref_box")] + \
+               [(n, i32) for n in ("S", "Rcap", "F", "N", "R", "B", "num_locs", "add_global", "target_kind", "num_labels")]
+
+
+class TaskImage(C.Structure):
+    _fields_ = [("feat_b64", c_p), ("feat_len", C.c_size_t), ("boxes_b64", c_p), ("boxes_len", C.c_size_t), ("feat", c_p), ("boxes", c_p),
+                ("rows", i32), ("F", i32)]
+
+
 class TailJob(C.Structure):
     _fields_ = [("dst", c_p), ("dst2", c_p), ("src", c_p), ("src2", c_p), ("stride", C.c_int64), ("n", C.c_int64), ("kind", i32), ("count", i32),
                 ("accumulate", i32), ("block_start", i32)]
@@ -266,6 +281,8 @@ _sig("vk_wordpiece_token_id", C.c_int, c_p, C.c_char_p)
 _sig("vk_wordpiece_encode", C.c_int, c_p, C.c_char_p, C.c_size_t, c_p, C.c_int)
 _sig("vk_wordpiece_encode_batch", C.c_int, c_p, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, c_p, C.c_int, c_p, C.c_int)
 _sig("vk_b64_decode", C.c_int, C.c_char_p, C.c_size_t, c_p, C.c_size_t, C.POINTER(C.c_size_t))
+_sig("vk_task_batch", C.c_int, C.POINTER(TaskBatchArgs), c_p)
+_sig("vk_task_images_stage", C.c_int, C.POINTER(TaskImage), C.c_int, C.c_int, C.POINTER(C.c_int))
 _sig("vk_vlbert_positions", C.c_int, c_p, C.c_int, C.c_int, C.c_int, c_p, c_p, c_p)
 _sig("vk_vis_loss_fwd", C.c_int, C.POINTER(VisLossArgs), c_p)
 _sig("vk_vis_loss_bwd", C.c_int, C.POINTER(VisLossArgs), c_p, C.c_int, c_p, c_p)
@@ -323,7 +340,8 @@ EXPORTS = ["vk_version", "vk_device_arch", "vk_last_error", "vk_set_seed", "vk_c
            "vk_mask_prep", "vk_mul_bf16", "vk_grad_norm_workspace_floats", "vk_grad_norm_clip", "vk_grad_norm_clip_masked", "vk_grad_sqnorm_chunks", "vk_grad_norm_from_chunks", "vk_adamw_step", "vk_adamw_step_on", "vk_adamw_step_list", "vk_grad_sqnorm_list", "vk_grad_sqnorm_list_work_floats", "vk_grad_seed", "vk_pair_gather", "vk_radam_step", "vk_radam_step_list",
            "vk_axpy_f32", "vk_sum_slabs_f32", "vk_sum_slabs_bf16", "vk_memset_async", "vk_hold_cus", "vk_gate_wait", "vk_bump_u64", "vk_store_u64", "vk_gate_value", "vk_comm_standin", "vk_gemm_reserve_cus", "vk_side_tail", "vk_run_ops", "vk_run_ops_timed", "vk_side_join", "vk_side_join_from", "vk_side_stream", "vk_side_enable", "vk_concap_batch",
            "vk_lmdb_open", "vk_lmdb_close", "vk_lmdb_entries", "vk_lmdb_first", "vk_lmdb_next", "vk_lmdb_get", "vk_concap_record_decode", "vk_concap_records_decode", "vk_b64_decode",
-           "vk_wordpiece_open", "vk_wordpiece_close", "vk_wordpiece_vocab_size", "vk_wordpiece_token_id", "vk_wordpiece_encode", "vk_wordpiece_encode_batch"]
+           "vk_wordpiece_open", "vk_wordpiece_close", "vk_wordpiece_vocab_size", "vk_wordpiece_token_id", "vk_wordpiece_encode", "vk_wordpiece_encode_batch",
+           "vk_task_batch", "vk_task_images_stage"]
 
 
 def check(rc):

@@ -594,3 +594,46 @@ extern "C" int vk_concap_records_decode(const void* const* recs, const size_t* l
     // re-run the failing record on this thread: deterministic, and leaves its message in this thread's vk_last_error()
     return vk_concap_record_decode(recs[bad.load()], lens[bad.load()], &slots[bad.load()]) ? -1 : set_error("vk_concap_records_decode: record %d failed", bad.load());
 }
+
+// ------------------------------------------------------------------------------------------------ task feature records
+// The two base64 fields of a batch of task-feature records into their staging slots.  Python has unpickled each record (the reference's
+// writers emit a plain dict of two ints and two text fields; pickle.loads hands the text over without a copy of ours) and knows the region
+// count from the text length, so all that is left is the decode -- the part that costs, and the part that runs without the GIL.
+static int task_image_stage(const vk_task_image* j) {
+    if (!j->feat_b64 || !j->boxes_b64 || !j->feat || !j->boxes || j->rows < 0 || j->F <= 0) return set_error("vk_task_images_stage: null field or bad shape");
+    size_t got = 0;
+    const size_t want_f = (size_t)j->rows * j->F * 4, want_b = (size_t)j->rows * 16;
+    if (vk_b64_decode(j->feat_b64, j->feat_len, j->feat, want_f, &got)) return -1;
+    if (got != want_f) return set_error("vk_task_images_stage: features decode to %zu bytes, %d rows of %d floats expected", got, j->rows, j->F);
+    if (vk_b64_decode(j->boxes_b64, j->boxes_len, j->boxes, want_b, &got)) return -1;
+    if (got != want_b) return set_error("vk_task_images_stage: boxes decode to %zu bytes, %d rows of 4 floats expected", got, j->rows);
+    return 0;
+}
+
+extern "C" int vk_task_images_stage(const vk_task_image* jobs, int n, int threads, int* failed) {
+    if (n <= 0) return 0;
+    if (!jobs) return set_error("vk_task_images_stage: null argument");
+    size_t dummy = 0;
+    char one[4];
+    vk_b64_decode("AAAA", 4, one, 4, &dummy);                        // builds the decode table before any thread starts
+    if (threads < 1) threads = 1;
+    if (threads > 16) threads = 16;
+    if (threads > n) threads = n;
+    if (failed) *failed = -1;
+    std::atomic<int> next{0}, bad{n};
+    auto work = [&]() {
+        for (int i = next.fetch_add(1); i < n; i = next.fetch_add(1)) {
+            if (task_image_stage(&jobs[i]) == 0) continue;
+            int cur = bad.load();
+            while (i < cur && !bad.compare_exchange_weak(cur, i)) {}
+        }
+    };
+    std::vector<std::thread> pool;
+    for (int t = 1; t < threads; ++t) pool.emplace_back(work);
+    work();
+    for (auto& th : pool) th.join();
+    if (bad.load() == n) return 0;
+    if (failed) *failed = bad.load();
+    // re-run the failing image on this thread: deterministic, and leaves its message in this thread's vk_last_error()
+    return task_image_stage(&jobs[bad.load()]) ? -1 : set_error("vk_task_images_stage: image %d failed", bad.load());
+}

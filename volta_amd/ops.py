@@ -203,3 +203,53 @@ def attn_bwd(a, dctx, dqkv, L, B, gate, H):
             b.dv[m] = t.data_ptr() + 2 * H * 2
             b.ldg[m] = 3 * H
     check(L_.lib.vk_gated_attn_bwd(C.byref(a), C.byref(b), stream_ptr()))
+
+
+GLOBAL_CODE = {None: 0, "first": 1, "last": 2}
+
+
+def task_batch(feat, boxes, n, wh, segs, mask_count, R, num_locs, add_global, scatter=None, ref_box=None, out=None, mean=None):
+    """vk_task_batch: staged images (feat [S, Rcap, F] fp32, boxes [S, Rcap, 4] fp32 pixels, n [S] int32, wh [S, 2] int32) and per output
+    block a segment list (segs [N, 2, 4] int32 = slot, src_from, dst_from, count) and a mask count (mask_count [N] int32) -> dict of
+    `features` [N, R, F], `spatials` [N, R, num_locs], `image_mask` [N, R] int64 and -- `scatter=(csr [B + 1] int32, labels int32, scores fp32,
+    num_labels)` -- `target` [B, num_labels], or -- `ref_box` [N, 4] fp32 pixels -- `target` [N, R, 1].  `out`: a dict of preallocated
+    outputs to write into (every element is written)."""
+    dev = feat.device
+    S, Rcap, F = feat.shape
+    N = segs.shape[0]
+    for t, dt, shape in ((feat, torch.float32, (S, Rcap, F)), (boxes, torch.float32, (S, Rcap, 4)), (n, torch.int32, (S,)), (wh, torch.int32, (S, 2)),
+                         (segs, torch.int32, (N, L.TASK_MAX_SEGS, 4)), (mask_count, torch.int32, (N,))):
+        assert t.is_cuda and t.dtype == dt and tuple(t.shape) == shape and t.is_contiguous(), (t.dtype, tuple(t.shape), shape)
+    assert F % 4 == 0 and num_locs in (4, 5) and R > 0 and add_global in GLOBAL_CODE
+    assert scatter is None or ref_box is None
+    out = dict(out) if out else {}
+
+    def buf(name, shape, dt):
+        t = out.get(name)
+        if t is None:
+            t = out[name] = torch.empty(shape, dtype=dt, device=dev)
+        assert t.is_cuda and t.dtype == dt and tuple(t.shape) == tuple(shape) and t.is_contiguous(), name
+        return t
+
+    features, spatials, image_mask = buf("features", (N, R, F), torch.float32), buf("spatials", (N, R, num_locs), torch.float32), buf("image_mask", (N, R), torch.int64)
+    a = L.TaskBatchArgs(ptr(feat), ptr(boxes), ptr(n), ptr(wh), None, ptr(segs), ptr(mask_count), ptr(features), ptr(spatials), ptr(image_mask))
+    a.S, a.Rcap, a.F, a.N, a.R, a.num_locs, a.add_global = S, Rcap, F, N, R, num_locs, GLOBAL_CODE[add_global]
+    if add_global is not None:
+        if mean is None:
+            mean = torch.empty(S, F, dtype=torch.float32, device=dev)
+        assert mean.is_cuda and mean.dtype == torch.float32 and mean.numel() >= S * F and mean.is_contiguous()
+        a.mean = ptr(mean)
+    if scatter is not None:
+        csr, labels, scores, num_labels = scatter
+        B = csr.numel() - 1
+        assert csr.dtype == torch.int32 and labels.dtype == torch.int32 and scores.dtype == torch.float32 and csr.is_cuda and labels.is_cuda and scores.is_cuda
+        assert B >= 0 and labels.numel() == scores.numel() and num_labels > 0
+        target = buf("target", (B, num_labels), torch.float32)
+        a.target, a.csr, a.labels, a.scores, a.B, a.num_labels, a.target_kind = ptr(target), ptr(csr), ptr(labels), ptr(scores), B, num_labels, L.TASK_TARGET_SCATTER
+    elif ref_box is not None:
+        assert ref_box.is_cuda and ref_box.dtype == torch.float32 and tuple(ref_box.shape) == (N, 4) and ref_box.is_contiguous()
+        target = buf("target", (N, R, 1), torch.float32)
+        a.target, a.ref_box, a.target_kind = ptr(target), ptr(ref_box), L.TASK_TARGET_IOU
+    check(L.lib.vk_task_batch(C.byref(a), stream_ptr()))
+    a._refs = (feat, boxes, n, wh, segs, mask_count, mean, scatter, ref_box)
+    return out

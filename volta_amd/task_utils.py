@@ -1,12 +1,16 @@
 """The step functions of the fine-tuning and evaluation drivers (volta/task_utils.py:24-281,429-618) without the reference's imports:
-`from volta_amd.task_utils import LoadLoss, ForwardModelsTrain, ForwardModelsVal, EvaluatingModel` in train_task.py:30 / eval_task.py:27.
+`from volta_amd.task_utils import LoadDataset, LoadLoss, ForwardModelsTrain, ForwardModelsVal` in train_task.py:30,
+`from volta_amd.task_utils import LoadDatasetEval, LoadLoss, ForwardModelsTrain, ForwardModelsVal, EvaluatingModel` in eval_task.py:27.
 
 With a volta_amd BertForVLTasks, a default nn.BCEWithLogitsLoss / nn.CrossEntropyLoss and a task type of the table below, model, loss
 and score run as ONE engine step (BertForVLTasks.task_loss: csrc/taskloss.hip reads the logits where the engine left them; loss and score
 stay on the device).  Every other combination -- V-logit-mc, a criterion with pos_weight / weight / label smoothing / another reduction,
 any other model object -- calls `model(...)` and does the reference's torch arithmetic, so the module replaces the reference's completely.
-VOLTA_TASK_LOSS=torch forces that path (the A/B switch of tools/bench_task_step.py).  The dataset loaders (LoadDataset, LoadDatasetEval) are
-host code over the feature readers and stay the reference's."""
+VOLTA_TASK_LOSS=torch forces that path (the A/B switch of tools/bench_task_step.py).
+
+LoadDataset / LoadDatasetEval (volta/task_utils.py:290-426) build the datasets of volta_amd.datasets over this project's readers and hand out
+`TaskLoader`s, which assemble the batches on the device (csrc/taskbatch.hip); VQA, GQA, NLVR2, refcoco / refcoco+ / refcocog and (training)
+RetrievalCOCO / RetrievalFlickr30k are covered, any other task name raises a KeyError that names the reference class to fall back to."""
 import os
 
 import torch
@@ -30,6 +34,88 @@ FUSED_KINDS = {
 
 def LoadLoss(task_cfg, task_id):
     return LossMap[task_cfg["TASK" + task_id]["loss"]]
+
+
+def _tokenizer(args):
+    """`BertTokenizer.from_pretrained(args.bert_model, do_lower_case=...)` for a model that is on disk: a directory holding vocab.txt, or the
+    vocabulary file itself.  Nothing is ever downloaded."""
+    from .readers import WordPieceTokenizer
+    name = str(args.bert_model)
+    if "roberta" in name:
+        raise ValueError("bert_model=%r: RoBERTa vocabularies are not supported; use the reference's loaders" % name)
+    path = os.path.join(name, "vocab.txt") if os.path.isdir(name) else name
+    if not os.path.isfile(path):
+        raise FileNotFoundError("bert_model=%r is neither a directory with a vocab.txt nor a vocabulary file; volta_amd does not download "
+                                "vocabularies -- point --bert_model at a local copy" % name)
+    return WordPieceTokenizer(path, do_lower_case=getattr(args, "do_lower_case", True))
+
+
+def _world(args):
+    import torch.distributed as dist
+    if args.local_rank == -1:
+        return 1, 0
+    return dist.get_world_size(), dist.get_rank()
+
+
+def _threads(args, world):
+    """the reference's worker arithmetic (num_workers / world size, task_utils.py:306-309) for the decode threads; None = the loader's default"""
+    return int((getattr(args, "num_workers", 0) or 0) / world) or None
+
+
+def _readers(args, config, cfg):
+    from .readers import ImageFeaturesH5Reader
+    return tuple(ImageFeaturesH5Reader(cfg[k], config, args.in_memory) if cfg[k] != "" else None for k in ("features_h5path1", "features_h5path2"))
+
+
+def _dataset(cls_map, args, config, cfg, readers, tokenizer, annotations, split):
+    return cls_map[cfg["name"]](task=cfg["name"], dataroot=cfg["dataroot"], annotations_jsonpath=annotations, split=split, image_features_reader=readers[0],
+                                gt_image_features_reader=readers[1], tokenizer=tokenizer, bert_model=args.bert_model, padding_index=0,
+                                max_seq_length=cfg["max_seq_length"], max_region_num=cfg["max_region_num"], num_locs=config.num_locs,
+                                add_global_imgfeat=config.add_global_imgfeat, append_mask_sep=(config.fusion_method == "vl-bert_vqa"))
+
+
+def LoadDataset(args, config, task_cfg, task_id, split="trainval"):
+    """-> (batch_size, task2num_iters, dset_train, dset_val, dl_train, dl_val) with the reference's batch-size arithmetic; the loaders are
+    volta_amd.datasets.TaskLoader: RandomSampler semantics without a process group, DistributedSampler semantics with one, sequential for
+    validation.  `args.seed` (default 0) seeds the permutations."""
+    from . import datasets as D
+    tokenizer = _tokenizer(args)
+    task = "TASK" + task_id
+    cfg = task_cfg[task]
+    readers = _readers(args, config, cfg)
+    world, rank = _world(args)
+    batch_size = cfg["batch_size"] // args.grad_acc_steps
+    if args.local_rank != -1:
+        batch_size = int(batch_size / world)
+    seed = int(getattr(args, "seed", 0) or 0)
+    kw = dict(drop_last=args.drop_last, in_memory=args.in_memory, threads=_threads(args, world))
+    dset_train, dl_train, task2num_iters = None, None, {}
+    if "train" in split:
+        dset_train = _dataset(D.DatasetMapTrain, args, config, cfg, readers, tokenizer, cfg["train_annotations_jsonpath"], cfg["train_split"])
+        sampler = D.RandomSampler(len(dset_train), seed) if args.local_rank == -1 else D.DistributedSampler(len(dset_train), world, rank, True, seed)
+        dl_train = D.TaskLoader(dset_train, batch_size, sampler, **kw)
+        task2num_iters = {task: len(dl_train)}
+    dset_val, dl_val = None, None
+    if "val" in split:
+        dset_val = _dataset(D.DatasetMapTrain, args, config, cfg, readers, tokenizer, cfg["val_annotations_jsonpath"], cfg["val_split"])
+        dl_val = D.TaskLoader(dset_val, batch_size, None, **kw)
+    return batch_size, task2num_iters, dset_train, dset_val, dl_train, dl_val
+
+
+def LoadDatasetEval(args, config, task_cfg, task_id):
+    """-> (batch_size, task2num_iters, dset_val, dl_val): `eval_batch_size` of the task (else args.batch_size), args.split over the task's val_split"""
+    from . import datasets as D
+    tokenizer = _tokenizer(args)
+    task = "TASK" + task_id
+    cfg = task_cfg[task]
+    readers = _readers(args, config, cfg)
+    batch_size = cfg.get("eval_batch_size", args.batch_size)
+    world = _world(args)[0]
+    if args.local_rank != -1:
+        batch_size = int(batch_size / world)
+    dset_val = _dataset(D.DatasetMapEval, args, config, cfg, readers, tokenizer, cfg["val_annotations_jsonpath"], args.split if args.split else cfg["val_split"])
+    dl_val = D.TaskLoader(dset_val, batch_size, None, drop_last=args.drop_last, in_memory=args.in_memory, threads=_threads(args, world))
+    return batch_size, {task: len(dl_val)}, dset_val, dl_val
 
 
 def compute_score_with_logits(logits, labels):
