@@ -203,14 +203,14 @@ typedef struct vk_ln_bwd_args {
     void* dz;              /* bf16 [M, H]: gradient w.r.t. z (= gradient of the residual branch and of addvec rows) */
     void* dd;              /* bf16 [M, H]: gradient w.r.t. d (pre-dropout mask re-applied); NULL: not needed */
     float* partial;        /* workspace fp32 [vk_ln_bwd_partial_rows(M), 2, H] */
-    float* dgamma;         /* [H] */
+    float* dgamma;         /* [H]  column sums over the job's rows: 0 for a job without rows (M <= 0 or *dyn == 0) */
     float* dbeta;          /* [H] */
     const int32_t* dyn;
     int32_t M, H;
     int32_t split_row;
     int32_t post;
     float out_scale;
-    int32_t accumulate;    /* bit 0: dgamma / dbeta += (shared sub-layers: one LayerNorm, two modalities);
+    int32_t accumulate;   /* bit 0: dgamma / dbeta += (shared sub-layers: one LayerNorm, two modalities);
                               bit 1: leave the column reduction of `partial` to a later vk_ln_bwd_finalize (same args) */
     vk_dropout drop;
     vk_drop_rows seg[2];

@@ -365,7 +365,6 @@ extern "C" int vk_ln_bwd_pair(const vk_ln_bwd_args* a, const vk_ln_bwd_args* b, 
     if (ln_check(a->H, 2048, "vk_ln_bwd")) return -1;
     if (b && (b->H != a->H || a->dyn || b->dyn)) return set_error("vk_ln_bwd_pair: both jobs need the same H and static row counts");
     const int nb0 = a->M > 0 ? vk_ln_bwd_partial_rows(a->M) : 0, nb1 = (b && b->M > 0) ? vk_ln_bwd_partial_rows(b->M) : 0;
-    if (nb0 + nb1 == 0) return 0;
     const int nch = (a->H + 255) / 256;
     dim3 grid(nb0 + nb1), block(LN_THREADS);
     hipStream_t s = (hipStream_t)stream;
@@ -374,7 +373,7 @@ extern "C" int vk_ln_bwd_pair(const vk_ln_bwd_args* a, const vk_ln_bwd_args* b, 
     jp.job[1] = b ? *b : *a;
     jp.nb0 = nb0;
     jp.stagger = g_ln_stagger; jp.stagger_mod = g_ln_stagger_mod;
-    switch (nch) {
+    if (nb0 + nb1) switch (nch) {
         case 1: hipLaunchKernelGGL(ln_bwd_kernel<1>, grid, block, 0, s, jp, g_ln_stamps); break;
         case 2: hipLaunchKernelGGL(ln_bwd_kernel<2>, grid, block, 0, s, jp, g_ln_stamps); break;
         case 3: hipLaunchKernelGGL(ln_bwd_kernel<3>, grid, block, 0, s, jp, g_ln_stamps); break;
@@ -382,15 +381,16 @@ extern "C" int vk_ln_bwd_pair(const vk_ln_bwd_args* a, const vk_ln_bwd_args* b, 
         case 5: case 6: hipLaunchKernelGGL(ln_bwd_kernel<6>, grid, block, 0, s, jp, g_ln_stamps); break;      // clf_hidden_size 1536 (task classifiers)
         default: hipLaunchKernelGGL(ln_bwd_kernel<8>, grid, block, 0, s, jp, g_ln_stamps); break;
     }
-    if (nb0 && !(a->accumulate & 2)) ln_finalize_launch(a, s);
-    if (nb1 && !(b->accumulate & 2)) ln_finalize_launch(b, s);
+    // a job without rows has no records: its finalize assigns the empty sum, 0 (nothing to do when it would only add it)
+    if ((nb0 || !(a->accumulate & 1)) && !(a->accumulate & 2)) ln_finalize_launch(a, s);
+    if (b && (nb1 || !(b->accumulate & 1)) && !(b->accumulate & 2)) ln_finalize_launch(b, s);
     return check_launch("vk_ln_bwd");
 }
 
 extern "C" int vk_ln_bwd(const vk_ln_bwd_args* a, vk_stream_t stream) { return vk_ln_bwd_pair(a, nullptr, stream); }
 
 extern "C" int vk_ln_bwd_finalize(const vk_ln_bwd_args* a, vk_stream_t stream) {
-    if (a->M <= 0) return 0;
+    if (a->M <= 0 && (a->accumulate & 1)) return 0;
     ln_finalize_launch(a, (hipStream_t)stream);
     return vk::check_launch("vk_ln_bwd_finalize");
 }
