@@ -530,7 +530,8 @@ int vk_adamw_step(const vk_adamw_args* a, vk_stream_t s);
  * for a step that runs on a stream of its own under the next forward pass, beside GEMM launches that claim the rest of the chip. */
 int vk_adamw_step_on(const vk_adamw_args* a, int ncus, vk_stream_t s);
 /* fp32 tensors OUTSIDE the arena (torch modules trained beside a volta_amd model, volta_amd/optimization.py): one descriptor per tensor,
- * contiguous, numel elements.  cls selects cls_lr_mult / cls_wd of the vk_adamw_args (VK_CHUNK_SKIP: not touched). */
+ * contiguous, numel elements.  cls selects cls_lr_mult / cls_wd of the vk_adamw_args; VK_CHUNK_SKIP and any class outside 0..7: not touched
+ * by vk_adamw_step_list. */
 typedef struct vk_adamw_tensor {
     float* p;
     const float* g;
@@ -544,7 +545,8 @@ typedef struct vk_adamw_tensor {
  * a's class arrays, lr, betas, eps, step_mult, grad_scale and clip; a->p / g / m / v / shadow / chunk_class / n are ignored.
  * max_numel: the largest numel in the list (sizes the grid). */
 int vk_adamw_step_list(const vk_adamw_args* a, const vk_adamw_tensor* list, int n, int64_t max_numel, vk_stream_t s);
-/* sums[t] = sum of squares of list[t].g (0 for cls == VK_CHUNK_SKIP), t < n, in a fixed order (no atomics, double partials): the slots behind an arena's
+/* sums[t] = sum of squares of list[t].g (0, and g not read, for cls == VK_CHUNK_SKIP alone: the descriptors also serve vk_radam_step_list,
+ * whose classes run to VK_RADAM_CLASSES, so every other class is summed), t < n, in a fixed order (no atomics, double partials): the slots behind an arena's
  * chunk sums for vk_grad_norm_from_chunks.  work: n * vk_grad_sqnorm_list_work_floats() floats of scratch. */
 int vk_grad_sqnorm_list(const vk_adamw_tensor* list, int n, int64_t max_numel, float* work, float* sums, vk_stream_t s);
 int vk_grad_sqnorm_list_work_floats(void);
@@ -578,11 +580,13 @@ int vk_radam_step(const vk_radam_args* a, vk_stream_t s);
 /* The same element function over `n` device descriptors of fp32 tensors OUTSIDE the arena (a torch head on a standalone BertModel) in ONE
  * launch; descriptor cls selects the class.  a->p / g / m / v / shadow / chunk_class / n are ignored; max_numel sizes the grid. */
 int vk_radam_step_list(const vk_radam_args* a, const vk_adamw_tensor* list, int n, int64_t max_numel, vk_stream_t s);
+/* y[i] += alpha * x[i], i < n (fp32).  n a multiple of 4; y and x 16-byte aligned (refused otherwise). */
 int vk_axpy_f32(float* y, const float* x, float alpha, int64_t n, vk_stream_t s);
 /* dst[i] = sum_{s < nslabs} src[s * slab_stride + i], i < n (fp32).  Combines the partial weight gradients of a
  * split-K wgrad: each K-chunk is an ordinary problem of the grouped TN launch writing its own slab. */
 int vk_sum_slabs_f32(float* dst, const float* src, int64_t slab_stride, int nslabs, int64_t n, vk_stream_t s);
-/* Same with a bf16 destination and a device-side row count: rows = min(*dyn_rows, n / row_len) rows of row_len. */
+/* Same with a bf16 destination and a device-side row count: rows = min(*dyn_rows, n / row_len) rows of row_len.  slab_stride, n and
+ * row_len multiples of 4; src 16-byte and dst 8-byte aligned (refused otherwise). */
 int vk_sum_slabs_bf16(void* dst, const float* src, int64_t slab_stride, int nslabs, int64_t n, const int32_t* dyn_rows, int row_len, vk_stream_t s);
 int vk_memset_async(void* p, int value, int64_t bytes, vk_stream_t s);
 /* No counterpart in the reference: `nwg` (<= 256) one-wave workgroups that stay resident for `usec` (<= 100000) microseconds.
@@ -633,7 +637,8 @@ typedef struct vk_tail_job {
 int vk_side_tail(const vk_tail_job* jobs, int njobs, vk_stream_t s);
 
 /* out[i] = a[i] * b[i] (bf16); processes rows * row_len elements where rows = min(*dyn_rows, n / row_len)
- * when dyn_rows != NULL.  (d gelu(u) = dz * gelu'(u) in the prediction-head transforms.) */
+ * when dyn_rows != NULL.  (d gelu(u) = dz * gelu'(u) in the prediction-head transforms.)  n and row_len multiples of 8; a, b and
+ * out 16-byte aligned (refused otherwise). */
 int vk_mul_bf16(const void* a, const void* b, void* out, int64_t n, const int32_t* dyn_rows, int row_len, vk_stream_t s);
 
 /* ------------------------------------------------------------------------------------------------

@@ -35,6 +35,7 @@ __global__ void mul_bf16_kernel(const uint16_t* a, const uint16_t* b, uint16_t* 
 extern "C" int vk_mul_bf16(const void* a, const void* b, void* out, int64_t n, const int32_t* dyn_rows, int row_len, vk_stream_t s) {
     if (n <= 0) return 0;
     if (n % 8 || row_len % 8) return vk::set_error("vk_mul_bf16: n and row_len must be multiples of 8");
+    if (((uintptr_t)a & 15) || ((uintptr_t)b & 15) || ((uintptr_t)out & 15)) return vk::set_error("vk_mul_bf16: 16-byte alignment required");
     int64_t blocks = (n / 8 + 255) / 256;
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(vk::mul_bf16_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)s, (const uint16_t*)a, (const uint16_t*)b,

@@ -206,7 +206,7 @@ __global__ __launch_bounds__(256) void sqnorm_list_partial_kernel(const vk_adamw
     __shared__ double sh[4];
     const vk_adamw_tensor t = list[blockIdx.y];
     double s = 0.0;
-    if (t.cls != VK_CHUNK_SKIP) {
+    if (t.cls != VK_CHUNK_SKIP) {               // any other class is summed: its range belongs to the optimizer that steps the list (8 for AdamW, VK_RADAM_CLASSES for RAdam)
         const bool vec = !((uintptr_t)t.g & 15);
         for (int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4; i < t.numel; i += (int64_t)gridDim.x * 1024) {
             if (vec && i + 4 <= t.numel) {
@@ -356,6 +356,7 @@ extern "C" int vk_side_tail(const vk_tail_job* jobs, int njobs, vk_stream_t s) {
 extern "C" int vk_sum_slabs_bf16(void* dst, const float* src, int64_t slab_stride, int nslabs, int64_t n, const int32_t* dyn_rows, int row_len, vk_stream_t s) {
     if (n <= 0 || nslabs <= 0) return 0;
     if ((slab_stride & 3) || (n & 3) || (row_len & 3)) return set_error("vk_sum_slabs_bf16: lengths must be multiples of 4");
+    if (((uintptr_t)src & 15) || ((uintptr_t)dst & 7)) return set_error("vk_sum_slabs_bf16: src needs 16-byte, dst 8-byte alignment");
     int64_t blocks = (n / 4 + 255) / 256;
     if (blocks > 2048) blocks = 2048;
     hipLaunchKernelGGL(sum_slabs_bf16_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)s, (uint16_t*)dst, src, (size_t)slab_stride, nslabs, (size_t)n, dyn_rows, row_len);
@@ -446,6 +447,7 @@ extern "C" int vk_grad_sqnorm_list(const vk_adamw_tensor* list, int n, int64_t m
 
 extern "C" int vk_axpy_f32(float* y, const float* x, float alpha, int64_t n, vk_stream_t s) {
     if (n % 4) return set_error("vk_axpy_f32: n %% 4 != 0");
+    if (((uintptr_t)y & 15) || ((uintptr_t)x & 15)) return set_error("vk_axpy_f32: 16-byte alignment required");
     if (n == 0) return 0;
     hipLaunchKernelGGL(axpy_kernel, dim3(2048), dim3(256), 0, (hipStream_t)s, y, x, alpha, (size_t)(n / 4));
     return check_launch("vk_axpy_f32");
