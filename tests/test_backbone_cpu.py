@@ -50,6 +50,33 @@ def test_standalone_is_a_root_model_and_refuses_cpu_execution():
     assert all(p._vk_owner is root for p in root.parameters())
 
 
+def test_plumbing_and_root_state_live_in_one_host_layer():
+    """The engine plumbing resolves through the MRO to the one base class, for each of the three root models, and a constructed root
+    model carries the whole root state while the BertModel nested in it carries none of it."""
+    from volta_amd.config import BertConfig
+    from volta_amd.modeling import BertForVLPreTraining, BertForVLTasks, BertModel, EngineHostModel
+    plumbing = ("materialize", "set_dropout_seed", "set_projection_dtype", "_engine", "_prep_inputs", "_engine_forward", "_backward_begin",
+                "_backward_run", "_run_step", "_init_root_state", "_adopt", "encode")
+    state = {"_vk_is_model", "_arena", "_engines", "_step", "_seed_base", "_last", "_ddp", "_fwd_serial", "_fp8", "_task_dropout"}
+    assert set(EngineHostModel._ROOT_STATE) == state
+    cfg = BertConfig.from_dict(dict(_configs()["gated"], clf_hidden_size=256))
+    for cls in (BertModel, BertForVLPreTraining, BertForVLTasks):
+        assert issubclass(cls, EngineHostModel)
+        for name in plumbing:
+            assert name not in cls.__dict__, (cls.__name__, name)
+            assert getattr(cls, name) is EngineHostModel.__dict__[name], (cls.__name__, name)
+        assert not getattr(cls, "_vk_is_model", False)
+    roots = [BertModel(cfg), BertForVLPreTraining(cfg), BertForVLTasks(cfg, {"TASK1": {"type": "VL-classifier", "num_labels": 5}}, ["TASK1"], dropout_prob=0.25)]
+    for root in roots:
+        assert state <= set(root.__dict__) and "_root" not in root.__dict__
+        assert (root._arena, root._engines, root._step, root._seed_base, root._last, root._ddp, root._fwd_serial, root._fp8) == (None, {}, 0, None, None, None, 0, False)
+        assert "_ddp" not in root._modules
+        if root is not roots[0]:
+            assert not state & set(root.bert.__dict__) and root.bert.__dict__["_root"] is root and "_root" not in root.bert._modules
+    assert roots[0]._engines is not roots[1]._engines
+    assert [r._task_dropout for r in roots] == [0.1, 0.1, 0.25]
+
+
 def test_from_pretrained_strips_the_bert_prefix(tmp_path):
     from volta_amd.config import BertConfig
     from volta_amd.modeling import BertForVLTasks, BertModel

@@ -84,6 +84,8 @@ class ParamArena:
         self.weights_epoch = 0          # bumped whenever the master weights changed (torch-side edits, fused AdamW)
         self.fp8_sites = {}             # data_ptr of an fp32 master view -> (view [N, K], q uint8 [N, Kp], scale [N])
         self.fp8_epoch = -1
+        self._plist = self._gviews = None       # param_list() / grad_views(), built on first use
+        self.opt_pending = None         # (range bounds, events) of a pipelined optimizer step still in flight (optimization.py)
 
     def view(self, name, which="master"):
         buf = getattr(self, which)
@@ -94,13 +96,13 @@ class ParamArena:
         return buf[o:o + n].view(self.shape[name])
 
     def param_list(self):
-        if getattr(self, "_plist", None) is None or len(self._plist) != len(self.params):
+        if self._plist is None or len(self._plist) != len(self.params):
             self._plist = list(self.params.items())
         return self._plist
 
     def grad_views(self):
         """One view of the gradient arena per parameter, created once (the hot loop only re-attaches them)."""
-        if getattr(self, "_gviews", None) is None or len(self._gviews) != len(self.params):
+        if self._gviews is None or len(self._gviews) != len(self.params):
             self._gviews = [self.view(n, "grad") for n in self.params]
         return self._gviews
 
@@ -163,7 +165,7 @@ class ParamArena:
 
     def sync_optimizer(self):
         """Make the current stream wait for a pipelined optimizer step still in flight on its own stream."""
-        pend = getattr(self, "opt_pending", None)
+        pend = self.opt_pending
         if pend:
             cur = torch.cuda.current_stream()
             for ev in pend[1]:
@@ -320,6 +322,18 @@ class StepEngine:
         self.inputs = {}              # name -> list of (struct, field) patched every step
         self.taps = {}
         self.grad_seeds = {}          # heads == "backbone": output name -> vk_grad_seed_args whose source bind_grads() patches every backward
+        self.losses = None            # heads == "pretrain": float[3] = lm, img, nsp, written by the forward list
+        self.nce_site = None          # dropout site of the nce_2048 negatives, where that visual target is configured
+        self.task_loss_bufs = None    # (work, out, amax) of vk_task_loss_fwd for this plan's logits (modeling._task_loss_args)
+        # builder state
+        self._aside = ""              # suffix of the temporaries of ops being built for a side-stream block (tmp)
+        self._split_cur = {}          # stream tag -> [bytes, counters] handed out to the split accumulations of the launch being built
+        self._soft_zero_b_listed = False
+        self._n_ln_partial = 0
+        self._deferred_ln = []        # LayerNorm backward arguments whose dgamma / dbeta reduction the next _wgrad() places
+        self._n_gate, self._gate_flag = 0, None
+        self._slab_cursor = 0
+        self._fwd_segments = {}       # fwd_segments() by optimizer range bounds
         self._build()
 
     # ---------------------------------------------------------------- helpers
@@ -338,7 +352,7 @@ class StepEngine:
     def tmp(self, name, shape, dtype=torch.bfloat16):
         """Backward temporaries are shared by all sub-layers (launches on one stream are ordered).  Ops that are being built for a
         side-stream block run NEXT to main-stream launches: they get temporaries of their own (`_aside`)."""
-        name += getattr(self, "_aside", "")
+        name += self._aside
         if name not in self.bufs:
             self.bufs[name] = torch.empty(shape, dtype=dtype, device=self.dev)
         t = self.bufs[name]
@@ -391,7 +405,7 @@ class StepEngine:
         tiles = C.c_int(0)
         nbytes = L.lib.vk_gemm_split_workspace_bytes(layout, M, N, nparts, geometry, C.byref(tiles))
         assert nbytes > 0 and tiles.value > 0, (layout, M, N, nparts, geometry)
-        aside, self._aside = getattr(self, "_aside", ""), ""          # the arenas belong to a stream, not to a block of ops
+        aside, self._aside = self._aside, ""          # the arenas belong to a stream, not to a block of ops
         if "split_ws_" + tag not in self.bufs:
             mb = os.environ.get("VK_SPLIT_WS_MB")
             cap = (int(mb) << 20) if mb else max(self.SPLIT_WS_MIN, _round_up(int(nbytes * 1.25), 1 << 20))
@@ -401,7 +415,7 @@ class StepEngine:
         if "split_cnt_" + tag not in self.bufs:
             self.bufs["split_cnt_" + tag] = torch.zeros(1 << 16, dtype=torch.int32, device=self.dev)      # zero once: every launch leaves them zero
         cnt = self.bufs["split_cnt_" + tag]
-        cur = self.__dict__.setdefault("_split_cur", {}).setdefault(tag, [0, 0])
+        cur = self._split_cur.setdefault(tag, [0, 0])
         if cur[0] + nbytes > ws.numel() or cur[1] + tiles.value > cnt.numel():
             raise RuntimeError("split-accumulation workspace too small (%d + %d of %d bytes): set VK_SPLIT_WS_MB" % (cur[0], nbytes, ws.numel()))
         out = (ws.data_ptr() + cur[0], cnt.data_ptr() + 4 * cur[1])
@@ -424,7 +438,7 @@ class StepEngine:
             cur = self._soft_cur_b
             self._soft_zero_b.p[0] = cnt.data_ptr() + 4 * cur
             self._soft_zero_b.n[0] = 4 * (self.SOFT_ROWS - cur)
-            if not getattr(self, "_soft_zero_b_listed", False):
+            if not self._soft_zero_b_listed:
                 self.bwd_pro.append((L.OP_GENERIC, 0, 0, 0, self._soft_zero_b, None, None))
                 self._soft_zero_b_listed = True
         else:
@@ -440,7 +454,7 @@ class StepEngine:
         return e | (int(self.bufs["gate_err"][0].item()) if "gate_err" in self.bufs else 0)
 
     def _split_launch_done(self, tag):
-        self.__dict__.setdefault("_split_cur", {})[tag] = [0, 0]
+        self._split_cur[tag] = [0, 0]
 
     @staticmethod
     def split_geometry(widths):
@@ -522,11 +536,11 @@ class StepEngine:
         block, next to main-stream LayerNorm backwards -- it cannot share their scratch records either."""
         H = H or self.H
         Hmax = max(self.st[0].H, self.st[1].H)
-        if (own_partial or getattr(self, "_aside", "")) and not defer:
-            self._n_ln_partial = getattr(self, "_n_ln_partial", 0) + 1
+        if (own_partial or self._aside) and not defer:
+            self._n_ln_partial += 1
             partial = self.buf("ln_partial_%d" % self._n_ln_partial, (L.lib.vk_ln_bwd_partial_rows(M) * 2 * H,), torch.float32)
         elif defer:
-            self._n_ln_partial = getattr(self, "_n_ln_partial", 0) + 1
+            self._n_ln_partial += 1
             partial = self.buf("ln_partial_%d" % self._n_ln_partial, (L.lib.vk_ln_bwd_partial_rows(M) * 2 * H,), torch.float32)
             accumulate |= 2
         else:
@@ -536,7 +550,7 @@ class StepEngine:
                         _mk_segs(drop, segs))
         a = self.k(a)
         if defer:
-            self._deferred_ln = getattr(self, "_deferred_ln", []) + [a]
+            self._deferred_ln.append(a)
         return a
 
     # ---------------------------------------------------------------- build
@@ -755,7 +769,7 @@ class StepEngine:
     # forward order) that transforms x[m] reads d(loss)/d(its output) from buffer k%2 and writes the gradient of
     # its input to buffer (k-1)%2; the embeddings read buffer 0, the heads fill buffer (final k)%2.
     def _dx(self, m, parity):
-        aside, self._aside = getattr(self, "_aside", ""), ""          # the hidden-state gradients are shared by definition
+        aside, self._aside = self._aside, ""          # the hidden-state gradients are shared by definition
         t = self.tmp("dx%d_%d" % (m, parity), (self.st[m].M, self.st[m].H))
         self._aside = aside
         return t
@@ -857,7 +871,7 @@ class StepEngine:
         # [H x F] output (24 tiles of 256 x 256) over B * Rv rows: row chunks as parts of one split accumulation fill the chip (146 -> 87 us, profiles/r03_ops_per_launch.txt)
         nparts = max(1, min(8, st.M // 1024))
         step = _round_up(-(-st.M // nparts), 64)
-        tag = "side" if getattr(self, "_aside", "") else "main"
+        tag = "side" if self._aside else "main"
         geo = self.split_geometry([F_])
         slices = [(_addr(dz[r0:]), _addr(featb[r0:]), min(step, st.M - r0), H, F_) for r0 in range(0, st.M, step)]
         probs = self.prob_parts(tag, geo, L.TN, slices, self.G(pre + wname + ".weight"), H, F_, F_, bias_grad=self.G(pre + wname + ".bias"))
@@ -1452,7 +1466,7 @@ class StepEngine:
         gate = self._gate_words() if self.side_gate else None
         b.append((L.OP_SIDE_BEGIN, 1 if gate is not None else 0, 0, 0, None, None, None))
         if gate is not None:
-            self._n_gate = getattr(self, "_n_gate", 0) + 1
+            self._n_gate += 1
             assert self._n_gate < gate.numel()
             flag = gate.data_ptr() + 8 * self._n_gate
             b.append((L.OP_GENERIC, 0, 0, 0, self.generic(L.FN_GATE, p=(flag, gate.data_ptr(), self.bufs["gate_err"]), n=(1000000,)), None, None))
@@ -1465,7 +1479,7 @@ class StepEngine:
         # every slab sum and every deferred LayerNorm dgamma / dbeta reduction of the sub-layer in ONE launch (vk_side_tail)
         jobs = [L.TailJob(_addr(dst), None, _addr(src), None, stride, n, 0, ns, 0, 0) for dst, src, stride, ns, n in reduces]
         by_dst = {}
-        for a in getattr(self, "_deferred_ln", []):          # LayerNorm parameter gradients of this sub-layer; a LayerNorm shared by both
+        for a in self._deferred_ln:          # LayerNorm parameter gradients of this sub-layer; a LayerNorm shared by both
             by_dst.setdefault(a.dgamma, []).append(a)         # modalities has two sets of partial records: ONE job sums both (no ordering between jobs)
         for group in by_dst.values():
             assert len(group) <= 2 and not (group[0].accumulate & 1) and all(g.accumulate & 1 for g in group[1:]), "unexpected LayerNorm sharing"
@@ -1495,7 +1509,7 @@ class StepEngine:
 
     def retire_on(self, probs):
         """Hang the pending gate flag on a launch's problem 0: its workgroups release the weight-gradient block as they retire."""
-        gf = getattr(self, "_gate_flag", None)
+        gf = self._gate_flag
         if gf is not None:
             probs[0].retire_flag, probs[0].retire_stamp = gf
             self._gate_flag = None
@@ -1505,8 +1519,7 @@ class StepEngine:
         """fp32 workspace for split-K partials; one arena reused by every sub-layer (launches are stream-ordered)."""
         cap = 48 * 3072 * 768
         ws = self.tmp("wgrad_slabs", (cap,), torch.float32)
-        cur = getattr(self, "_slab_cursor", 0)
-        cur = _round_up(cur, 4)
+        cur = _round_up(self._slab_cursor, 4)
         assert cur + n <= cap, "wgrad slab workspace too small"
         self._slab_cursor = cur + n
         return ws[cur:cur + n]
@@ -1932,7 +1945,7 @@ class StepEngine:
         encoder sub-layer, sub-layer n its own slots, the heads (poolers, cls.*, the tied decoder) everything."""
         arena = self.arena
         key = tuple(bounds)
-        cache = self.__dict__.setdefault("_fwd_segments", {})
+        cache = self._fwd_segments
         if key in cache:
             return cache[key]
 
@@ -1961,7 +1974,7 @@ class StepEngine:
     def run_forward(self):
         """The forward list; when a pipelined optimizer (AdamW(overlap_with_forward=True)) is still walking the arena on its own stream,
         every segment first waits for the ranges whose weights it reads."""
-        pend = getattr(self.arena, "opt_pending", None)
+        pend = self.arena.opt_pending
         if not pend:
             self.fwd.run()
             return
@@ -1988,7 +2001,7 @@ class StepEngine:
                     getattr(struct, field)[index] = addr
 
     def prepare_step(self, seed):
-        if self.train or getattr(self, "nce_site", None) is not None:      # nce_2048 draws its negatives in eval mode too
+        if self.train or self.nce_site is not None:      # nce_2048 draws its negatives in eval mode too
             check(L.lib.vk_set_seed(ptr(self.seed), C.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), L.stream_ptr()))
 
 

@@ -173,25 +173,239 @@ class BertEncoder(M.Holder):
         self.layer = nn.ModuleList(layers)
 
 
+class EngineHostModel(PreTrainedModel):
+    """What BertModel, BertForVLPreTraining and BertForVLTasks share as root models: the state of a root model (`_ROOT_STATE`), the flat
+    parameter arena, the cache of engine plans and the host side of one engine step.  The model that holds another one takes its
+    parameters and its root state (`_adopt`); the nested model keeps `_root` only."""
+
+    _heads_mode = "pretrain"           # StepEngine(heads=...)
+    _torch_param_prefixes = ()         # parameters of torch-side head modules: autograd, not the engine, writes their gradients
+    task_cfg = None
+    # `_vk_is_model` lets clip_grad_norm_(model.parameters()) recognise the whole arena without walking it: on the instance, a nested model is none
+    _ROOT_STATE = dict(_vk_is_model=True, _arena=None, _engines=None, _step=0, _seed_base=None, _last=None, _ddp=None, _fwd_serial=0,
+                       _fp8=False, _task_dropout=0.1)
+
+    def _init_root_state(self, task_dropout=0.1):
+        """Last step of a root model's constructor.  `_root` and `_ddp` are modules: in `__dict__`, out of nn.Module's registration."""
+        self.add_global_imgfeat = int(self.config.add_global_imgfeat is not None)
+        self.__dict__.update(self._ROOT_STATE, _engines={}, _task_dropout=float(task_dropout))
+        for mod in self.modules():
+            if mod is not self and isinstance(mod, EngineHostModel):
+                mod._adopt(self)
+        for p in self.parameters():            # lets an optimizer find (and materialize) its model before the first forward,
+            p._vk_owner = self                 # e.g. AdamW.load_state_dict() in the reference's resume() order
+
+    def _adopt(self, root):
+        """Called by the root model that holds this one: the parameters become the root's, the standalone state goes."""
+        self.__dict__["_root"] = root
+        for k in self._ROOT_STATE:
+            self.__dict__.pop(k, None)
+
+    def set_dropout_seed(self, seed):
+        self._seed_base, self._step = int(seed), 0
+
+    def set_projection_dtype(self, dtype):
+        """"bf16" (default) or "fp8": run the forward Q|K|V / FFN projections of the encoder on the e4m3 MFMA path (csrc/fp8.hip)."""
+        if dtype not in ("bf16", "fp8"):
+            raise ValueError("projection dtype %r (bf16 | fp8)" % (dtype,))
+        self._fp8 = dtype == "fp8"
+
+    def materialize(self, device=None):
+        """Build (or rebuild) the flat parameter arenas on `device`; parameters become views of them.  (Nested: the root model's.)"""
+        root = self.__dict__.get("_root")
+        if root is not None:
+            return root.materialize(device)
+        from .engine import ParamArena
+        dev = torch.device(device) if device is not None else next(self.parameters()).device
+        if dev.type != "cuda":
+            raise RuntimeError("volta_amd runs on an MI355X only: move the model to the GPU first (model.cuda()); "
+                               "there is no CPU execution path")
+        arena = self._arena
+        if arena is None or arena.device != dev or not arena.intact():
+            self._arena, self._engines = ParamArena(self, dev, prefix=self._arena_prefix), {}
+            for p in self.parameters():
+                p._vk_owner = self
+        return self._arena
+
+    def _engine(self, B, T, Rv, train, task_id=None, maps=False):
+        from .engine import StepEngine
+        arena = self.materialize()
+        key = (B, T, Rv, bool(train), self._fp8, task_id, maps)
+        eng = self._engines.get(key)
+        if eng is None:
+            for k in [k for k in self._engines if k[3] == key[3] and k[5] == task_id and k[6] == maps]:      # one plan per mode (and task head) keeps memory bounded
+                del self._engines[k]
+            task = (task_id, self.task_cfg[task_id]) if task_id is not None else None
+            eng = StepEngine(self.config, arena, B, T, Rv, train, heads=self._heads_mode, fp8=self._fp8, task=task,
+                             task_dropout=self._task_dropout, attn_maps=maps)
+            self._engines[key] = eng
+        return eng
+
+    def _prep_inputs(self, input_ids, image_feat, image_loc, token_type_ids, attention_mask, image_attention_mask,
+                     masked_lm_labels=None, image_label=None, image_cls=None, next_sentence_label=None, obj_labels=None, obj_confs=None,
+                     attr_labels=None, attr_confs=None):
+        dev = next(self.parameters()).device
+        B, T = input_ids.shape
+        Rv = image_feat.shape[1]
+        i64 = dict(device=dev, dtype=torch.int64)
+        f32 = dict(device=dev, dtype=torch.float32)
+        if attention_mask is None:
+            attention_mask = torch.ones(B, T, **i64)
+        if token_type_ids is None:
+            token_type_ids = torch.zeros(B, T, **i64)
+        if image_attention_mask is None:
+            image_attention_mask = torch.ones(B, Rv, **i64)
+        R = Rv - self.add_global_imgfeat
+        t = dict(input_ids=input_ids.to(**i64).contiguous(), token_type_ids=token_type_ids.to(**i64).contiguous(),
+                 attention_mask=attention_mask.to(**i64).contiguous(), image_attention_mask=image_attention_mask.to(**i64).contiguous(),
+                 image_feat=image_feat.to(**f32).contiguous(), image_loc=image_loc.to(**f32).contiguous())
+        assert t["image_feat"].shape == (B, Rv, self.config.v_feature_size), "image_feat must be [B, regions, v_feature_size]"
+        assert t["image_loc"].shape == (B, Rv, self.config.num_locs), "image_loc must be [B, regions, num_locs]"
+        if masked_lm_labels is not None:
+            t["masked_lm_labels"] = masked_lm_labels.to(**i64).contiguous()
+            t["image_label"] = image_label.to(**i64).contiguous()
+            assert t["masked_lm_labels"].shape == (B, T) and t["image_label"].shape == (B, R)
+            # what each configured visual target reads (volta/losses.py); the reference silently drops a target whose inputs are
+            # missing -- here that is an error, the plan was compiled for the configured targets
+            need = set()
+            for ix, w in self.config.visual_target_weights.items():
+                if w > 0:
+                    need |= {"0": {"image_cls"}, "3": {"obj_labels", "obj_confs"}, "4": {"attr_labels", "attr_confs"}, "6": {"obj_labels"}}.get(ix, set())
+            given = dict(image_cls=image_cls, obj_labels=obj_labels, obj_confs=obj_confs, attr_labels=attr_labels, attr_confs=attr_confs)
+            for name in sorted(need):
+                if given[name] is None:
+                    raise ValueError("visual target weights %r need `%s`" % (self.config.visual_target_weights, name))
+                x = given[name].to(**(i64 if name.endswith("labels") else f32)).contiguous()
+                assert x.shape[:2] == (B, R), "%s must be [B, regions%s]" % (name, ", 1601" if name == "image_cls" else "")
+                t[name] = x
+            if "image_cls" in t:
+                assert t["image_cls"].shape == (B, R, 1601)
+            if self.config.fusion_method in ("mul", "sum", "text"):
+                if next_sentence_label is None:
+                    raise ValueError("fusion method %r has an ITM head: next_sentence_label is required" % self.config.fusion_method)
+                t["next_sentence_label"] = next_sentence_label.to(**i64).contiguous()
+                assert t["next_sentence_label"].numel() == B
+            # ids / labels are range-clamped inside the kernels: no host synchronisation on the hot path
+        return t, B, T, Rv
+
+    def _engine_forward(self, tensors, task_id=None, attn_maps=False):
+        """One forward list: the plan of this shape and mode, with `task_id`'s classifier behind the poolers and, with `attn_maps`, every
+        attention sub-layer's probabilities kept.  Returns the pre-training losses (None on the other plans)."""
+        B, T = tensors["input_ids"].shape
+        Rv = tensors["image_feat"].shape[1]
+        eng = self._engine(B, T, Rv, self.training, task_id, bool(attn_maps))
+        eng.arena.refresh_shadow()
+        if eng.fp8:
+            eng.arena.sync_optimizer()         # the re-quantisation reads the fp32 masters
+            eng.arena.refresh_fp8()
+        eng.bind_inputs(tensors)
+        if self._seed_base is None:
+            self._seed_base = int(torch.initial_seed())
+        eng.prepare_step(self._seed_base + self._step)
+        self._step += 1
+        eng.run_forward()
+        self._last = (eng, tensors)      # keeps the step's input tensors alive until backward
+        return eng.losses
+
+    def _run_step(self, node, eager, *args):
+        """One step on *args: as the autograd node `node` (an autograd.Function taking model, anchor parameter, *args) when autograd is on
+        and a parameter wants a gradient, as `eager(*args)` under no_grad otherwise (always, with node None)."""
+        self.materialize()
+        anchor = next((p for p in self.parameters() if p.requires_grad), None) if node is not None and torch.is_grad_enabled() else None
+        if anchor is not None:
+            return node.apply(self, anchor, *args)
+        with torch.no_grad():
+            return eager(*args)
+
+    def _backward_begin(self, eng, absent=()):
+        """Gradient-accumulation bookkeeping shared by the root models.  Parameters of torch-side head modules (`_torch_param_prefixes`) get
+        their gradients from autograd (redirected into the arena by a hook).  `absent`: arena names that receive no gradient in this
+        backward (a standalone BertModel's pooler whose output got none) -- left as they are, like `unused_params`."""
+        arena = eng.arena
+        from .optimization import flush_clip
+        flush_clip(arena)                   # a clip coefficient no optimizer step has consumed applies to the gradients it was computed for
+        skip = self._torch_param_prefixes
+        # frozen parameters (requires_grad False: volta/train_utils.py:250-255) get no .grad, as under autograd; the
+        # optimizer and clip_grad_norm_ then leave their arena chunks alone
+        unused = eng.unused_params          # e.g. the VQA text pooler in pre-training: no launch reads it, .grad stays None
+        pairs = [((n, p), g) for (n, p), g in zip(arena.param_list(), arena.grad_views())
+                 if p.requires_grad and not (skip and n.startswith(skip)) and n not in unused and n not in absent]
+        params, gviews = [x[0] for x in pairs], [x[1] for x in pairs]
+        n_have = sum(p.grad is not None for _, p in params)
+        accumulate = n_have == len(params)
+        if n_have and not accumulate:
+            raise RuntimeError("volta_amd: some parameters carry a .grad and some do not; zero_grad() all of them")
+        old = None
+        if accumulate:
+            if not all(p.grad is g or p.grad.data_ptr() == g.data_ptr() for (_, p), g in zip(params, gviews)):
+                raise RuntimeError("volta_amd: .grad tensors were replaced by foreign tensors; call zero_grad(set_to_none=True)")
+            old = arena.grad.clone()
+        return params, gviews, accumulate, old
+
+    def _backward_run(self, eng, state):
+        params, gviews, accumulate, old = state
+        arena = eng.arena
+        skip = self._torch_param_prefixes
+        if skip:            # the engine list zero-fills / overwrites only what it owns; torch-side head gradients are already in the arena
+            keep = [(g, g.clone()) for (n, _), g in zip(arena.param_list(), arena.grad_views()) if n.startswith(skip)] if accumulate else []
+        ddp = self._ddp
+        if ddp is not None:
+            ddp.run_backward(eng)
+        else:
+            eng.bwd.run()
+        if accumulate:
+            from . import _lib as L
+            L.check(L.lib.vk_axpy_f32(L.ptr(arena.grad), L.ptr(old), 1.0, arena.total, L.stream_ptr()))
+            if skip:
+                for g, saved in keep:
+                    g.copy_(saved)
+        else:
+            for (_, p), g in zip(params, gviews):
+                p.grad = g
+
+    def _encode_labels(self, B, T, R, dev):
+        """Label tensors the plan that encode() runs reads besides the inputs (the pre-training plan: dummies)."""
+        return {}
+
+    def encode(self, input_ids, image_feat, image_loc, token_type_ids=None, attention_mask=None, image_attention_mask=None,
+               output_all_encoded_layers=False, output_all_attention_masks=False):
+        """A nested BertModel's forward, without gradient: (seq_t [B,T,H], seq_v [B,Rv,Hv], pooled_t, pooled_v, attention maps = ([], []));
+        with `output_all_encoded_layers` the two sequences are lists with both streams' states after EVERY sub-layer (encoders.py:868-881)."""
+        B, T = input_ids.shape
+        labels = self._encode_labels(B, T, image_feat.shape[1] - self.add_global_imgfeat, next(self.parameters()).device)
+        tensors, B, T, Rv = self._prep_inputs(input_ids, image_feat, image_loc, token_type_ids, attention_mask, image_attention_mask, **labels)
+        self._run_step(None, self._engine_forward, tensors, None, output_all_attention_masks and self.config.visualization)
+        eng = self._last[0]
+        attn_maps = _attention_maps(self.config, eng, output_all_attention_masks)
+        H, Hv = self.config.hidden_size, self.config.v_hidden_size
+        pt, pv = eng.taps["pooled_t"], eng.taps["pooled_v"]          # None where the fusion method has no such pooler
+        if output_all_encoded_layers:
+            seq_t = [eng.taps["t%d" % n].view(B, T, H).float() for n in eng.sublayer_ids]
+            seq_v = [eng.taps["v%d" % n].view(B, Rv, Hv).float() for n in eng.sublayer_ids]
+        else:
+            seq_t, seq_v = eng.taps["seq_t"].view(B, T, H).float(), eng.taps["seq_v"].view(B, Rv, Hv).float()
+        return seq_t, seq_v, None if pt is None else pt.float(), None if pv is None else pv.float(), attn_maps
+
+
 class _BackboneStep(torch.autograd.Function):
     """A standalone BertModel's forward as one autograd node.  Outputs (fp32): the final text / vision states, the pooled vectors the fusion
     method has, then with output_all_encoded_layers the states after every sub-layer but the last.  Their gradients re-enter the engine as
     the seeds of its backward list; a gradient autograd does not materialise (None) costs no pass."""
 
     @staticmethod
-    def forward(ctx, model, anchor, tensors, all_layers):
+    def forward(ctx, model, anchor, tensors, all_layers, maps):
         ctx.set_materialize_grads(False)
-        outs = model._backbone_forward(tensors, all_layers)
+        outs = model._backbone_forward(tensors, all_layers, maps)
         ctx.model, ctx.serial, ctx.names = model, model._fwd_serial, [n for n, _ in outs]
         return tuple(t for _, t in outs)
 
     @staticmethod
     def backward(ctx, *grads):
         ctx.model._backbone_backward(ctx, dict(zip(ctx.names, grads)))
-        return None, None, None, None
+        return None, None, None, None, None
 
 
-class BertModel(PreTrainedModel):
+class BertModel(EngineHostModel):
     """Embeddings + gated encoder + poolers (volta/encoders.py:918-1017).
 
     Inside BertForVLPreTraining / BertForVLTasks it is the parameter container of the root model, and `forward` is the root's `encode()`
@@ -230,11 +444,7 @@ class BertModel(PreTrainedModel):
             self.v_pooler.add_module("dense", M.LinearParams(config.v_hidden_size, config.v_pooler_size))
         M.init_bert_(self, config.initializer_range)
         M.special_init_embeddings_(self.embeddings, kind, config)
-        # root-model state; a root model that builds this BertModel takes its parameters and removes the flag (_adopt)
-        self.add_global_imgfeat = int(config.add_global_imgfeat is not None)
-        self.__dict__.update(_vk_is_model=True, _arena=None, _engines={}, _step=0, _seed_base=None, _last=None, _ddp=None, _fwd_serial=0)
-        for p in self.parameters():
-            p._vk_owner = self
+        self._init_root_state()          # a root model that builds this BertModel takes its parameters and this state (_adopt)
 
     def forward(self, input_txt, input_imgs, image_loc, token_type_ids=None, attention_mask=None,
                 image_attention_mask=None, output_all_encoded_layers=False, output_all_attention_masks=False):
@@ -246,26 +456,12 @@ class BertModel(PreTrainedModel):
         if root is not None:
             return root.encode(input_txt, input_imgs, image_loc, token_type_ids, attention_mask, image_attention_mask,
                                output_all_encoded_layers=output_all_encoded_layers, output_all_attention_masks=output_all_attention_masks)
-        tensors, B, T, Rv = self._prep_inputs(input_txt, input_imgs, image_loc, token_type_ids, attention_mask, image_attention_mask,
-                                              None, None, None, None)
+        tensors, B, T, Rv = self._prep_inputs(input_txt, input_imgs, image_loc, token_type_ids, attention_mask, image_attention_mask)
         all_layers = bool(output_all_encoded_layers)
-        self.__dict__["_want_attn_maps"] = bool(output_all_attention_masks and self.config.visualization)
-        try:
-            self.materialize()
-            from .optimization import flush_clip
-            flush_clip(self._arena)      # a pending clip coefficient belongs to the gradients as they are now, before autograd adds to any of them
-            if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-                anchor = next(p for p in self.parameters() if p.requires_grad)
-                flat = _BackboneStep.apply(self, anchor, tensors, all_layers)
-                names = [n for n, _ in self._backbone_outputs(self._last[0], all_layers)]
-            else:
-                with torch.no_grad():
-                    outs = self._backbone_forward(tensors, all_layers)
-                names, flat = [n for n, _ in outs], [t for _, t in outs]
-        finally:
-            self.__dict__["_want_attn_maps"] = False
-        out = dict(zip(names, flat))
+        maps = bool(output_all_attention_masks and self.config.visualization)
+        flat = self._run_step(_BackboneStep, lambda *a: [t for _, t in self._backbone_forward(*a)], tensors, all_layers, maps)
         eng = self._last[0]
+        out = dict(zip([n for n, _ in self._backbone_outputs(eng, all_layers)], flat))
         attn_maps = _attention_maps(self.config, eng, output_all_attention_masks)
         if all_layers:
             last = eng.sublayer_ids[-1]
@@ -276,12 +472,6 @@ class BertModel(PreTrainedModel):
         return seq_t, seq_v, out.get("pooled_t"), out.get("pooled_v"), attn_maps
 
     # ------------------------------------------------------------------ standalone root model
-    def _adopt(self, root):
-        """Called by the root model that holds this BertModel: the parameters become the root's, the standalone state goes."""
-        self.__dict__["_root"] = root
-        for k in ("_vk_is_model", "_arena", "_engines", "_step", "_seed_base", "_last", "_ddp", "_fwd_serial"):
-            self.__dict__.pop(k, None)
-
     def _backbone_outputs(self, eng, all_layers):
         """[(output name, bf16 engine buffer)] in the order of _BackboneStep's outputs."""
         B, T, Rv = eng.B, eng.T, eng.Rv
@@ -293,9 +483,11 @@ class BertModel(PreTrainedModel):
             outs += [("t%d" % n, eng.taps["t%d" % n].view(B, T, H)) for n in ids] + [("v%d" % n, eng.taps["v%d" % n].view(B, Rv, Hv)) for n in ids]
         return outs
 
-    def _backbone_forward(self, tensors, all_layers):
-        self._engine_forward(tensors)
-        self.__dict__["_fwd_serial"] += 1
+    def _backbone_forward(self, tensors, all_layers, maps):
+        from .optimization import flush_clip
+        flush_clip(self._arena)      # a pending clip coefficient belongs to the gradients as they are now, before autograd adds to any of them
+        self._engine_forward(tensors, attn_maps=maps)
+        self._fwd_serial += 1
         return [(n, t.float()) for n, t in self._backbone_outputs(self._last[0], all_layers)]
 
     def _backbone_backward(self, ctx, grads):
@@ -352,9 +544,8 @@ class _PretrainStep(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, model, anchor, tensors):
-        losses = model._engine_forward(tensors)
         ctx.model = model
-        return losses[0:1].clone(), losses[1:2].clone(), losses[2:3].clone()
+        return model._losses(tensors)
 
     @staticmethod
     def backward(ctx, g_lm, g_img, g_nsp):
@@ -362,7 +553,7 @@ class _PretrainStep(torch.autograd.Function):
         return None, None, None
 
 
-class BertForVLPreTraining(PreTrainedModel):
+class BertForVLPreTraining(EngineHostModel):
     """BERT model with multimodal pre-training heads (volta/encoders.py:1020-1114)."""
 
     def __init__(self, config):
@@ -371,184 +562,21 @@ class BertForVLPreTraining(PreTrainedModel):
         self.cls = BertPreTrainingHeads(config, self.bert.embeddings.word_embeddings.weight)
         self.visual_target_weights = config.visual_target_weights
         logger.info("model's visual targets are %s", [ix for ix, w in config.visual_target_weights.items() if w > 0])
-        self.add_global_imgfeat = int(config.add_global_imgfeat is not None)
         self.tie_weights()
-        self.__dict__["_arena"] = None
-        self.__dict__["_engines"] = {}
-        self.__dict__["_step"] = 0
-        self.__dict__["_seed_base"] = None
-        self.__dict__["_last"] = None
-        self.__dict__["_ddp"] = None
-        self.bert._adopt(self)
-        for mod in self.modules():
-            if mod is not self and isinstance(mod, PreTrainedModel):
-                mod.__dict__["_root"] = self
-        for p in self.parameters():            # lets an optimizer find (and materialize) its model before the first forward,
-            p._vk_owner = self                 # e.g. AdamW.load_state_dict() in the reference's resume() order
+        self._init_root_state()
 
     def tie_weights(self):
         self._tie_or_clone_weights(self.cls.predictions.decoder, self.bert.embeddings.word_embeddings)
 
-    # ------------------------------------------------------------------ engine plumbing
-    def set_dropout_seed(self, seed):
-        self.__dict__["_seed_base"] = int(seed)
-        self.__dict__["_step"] = 0
-
-    _vk_is_model = True      # lets clip_grad_norm_(model.parameters()) recognise the whole arena without walking it
-
-    def materialize(self, device=None):
-        """Build (or rebuild) the flat parameter arenas on `device`; parameters become views of them."""
-        from .engine import ParamArena
-        dev = torch.device(device) if device is not None else next(self.parameters()).device
-        if dev.type != "cuda":
-            raise RuntimeError("volta_amd runs on an MI355X only: move the model to the GPU first (model.cuda()); "
-                               "there is no CPU execution path")
-        arena = self.__dict__.get("_arena")
-        if arena is None or arena.device != dev or not arena.intact():
-            self.__dict__["_arena"] = ParamArena(self, dev, prefix=self._arena_prefix)
-            self.__dict__["_engines"] = {}
-            for p in self.parameters():
-                p._vk_owner = self
-        return self.__dict__["_arena"]
-
-    def _engine(self, B, T, Rv, train):
-        from .engine import StepEngine
-        arena = self.materialize()
-        fp8 = bool(self.__dict__.get("_fp8", False))
-        task_id = self.__dict__.get("_cur_task")
-        maps = bool(self.__dict__.get("_want_attn_maps", False))
-        key = (B, T, Rv, bool(train), fp8, task_id, maps)
-        eng = self._engines.get(key)
-        if eng is None:
-            for k in [k for k in self._engines if k[3] == key[3] and k[5] == task_id and k[6] == maps]:      # one plan per mode (and task head) keeps memory bounded
-                del self._engines[k]
-            task = (task_id, self.task_cfg[task_id]) if task_id is not None else None
-            eng = StepEngine(self.config, arena, B, T, Rv, train, heads=getattr(self, "_heads_mode", "pretrain"), fp8=fp8, task=task,
-                             task_dropout=self.__dict__.get("_task_dropout", 0.1), attn_maps=maps)
-            self._engines[key] = eng
-        return eng
-
-    def set_projection_dtype(self, dtype):
-        """"bf16" (default) or "fp8": run the forward Q|K|V / FFN projections of the encoder on the e4m3 MFMA path (csrc/fp8.hip)."""
-        if dtype not in ("bf16", "fp8"):
-            raise ValueError("projection dtype %r (bf16 | fp8)" % (dtype,))
-        self.__dict__["_fp8"] = dtype == "fp8"
-
-    def _prep_inputs(self, input_ids, image_feat, image_loc, token_type_ids, attention_mask, image_attention_mask,
-                     masked_lm_labels, image_label, image_cls, next_sentence_label, obj_labels=None, obj_confs=None,
-                     attr_labels=None, attr_confs=None):
-        dev = next(self.parameters()).device
-        B, T = input_ids.shape
-        Rv = image_feat.shape[1]
-        i64 = dict(device=dev, dtype=torch.int64)
-        f32 = dict(device=dev, dtype=torch.float32)
-        if attention_mask is None:
-            attention_mask = torch.ones(B, T, **i64)
-        if token_type_ids is None:
-            token_type_ids = torch.zeros(B, T, **i64)
-        if image_attention_mask is None:
-            image_attention_mask = torch.ones(B, Rv, **i64)
-        R = Rv - self.add_global_imgfeat
-        t = dict(input_ids=input_ids.to(**i64).contiguous(), token_type_ids=token_type_ids.to(**i64).contiguous(),
-                 attention_mask=attention_mask.to(**i64).contiguous(), image_attention_mask=image_attention_mask.to(**i64).contiguous(),
-                 image_feat=image_feat.to(**f32).contiguous(), image_loc=image_loc.to(**f32).contiguous())
-        assert t["image_feat"].shape == (B, Rv, self.config.v_feature_size), "image_feat must be [B, regions, v_feature_size]"
-        assert t["image_loc"].shape == (B, Rv, self.config.num_locs), "image_loc must be [B, regions, num_locs]"
-        if masked_lm_labels is not None:
-            t["masked_lm_labels"] = masked_lm_labels.to(**i64).contiguous()
-            t["image_label"] = image_label.to(**i64).contiguous()
-            assert t["masked_lm_labels"].shape == (B, T) and t["image_label"].shape == (B, R)
-            # what each configured visual target reads (volta/losses.py); the reference silently drops a target whose inputs are
-            # missing -- here that is an error, the plan was compiled for the configured targets
-            need = set()
-            for ix, w in self.config.visual_target_weights.items():
-                if w > 0:
-                    need |= {"0": {"image_cls"}, "3": {"obj_labels", "obj_confs"}, "4": {"attr_labels", "attr_confs"}, "6": {"obj_labels"}}.get(ix, set())
-            given = dict(image_cls=image_cls, obj_labels=obj_labels, obj_confs=obj_confs, attr_labels=attr_labels, attr_confs=attr_confs)
-            for name in sorted(need):
-                if given[name] is None:
-                    raise ValueError("visual target weights %r need `%s`" % (self.config.visual_target_weights, name))
-                x = given[name].to(**(i64 if name.endswith("labels") else f32)).contiguous()
-                assert x.shape[:2] == (B, R), "%s must be [B, regions%s]" % (name, ", 1601" if name == "image_cls" else "")
-                t[name] = x
-            if "image_cls" in t:
-                assert t["image_cls"].shape == (B, R, 1601)
-            if self.bert.fusion_method in ("mul", "sum", "text"):
-                if next_sentence_label is None:
-                    raise ValueError("fusion method %r has an ITM head: next_sentence_label is required" % self.bert.fusion_method)
-                t["next_sentence_label"] = next_sentence_label.to(**i64).contiguous()
-                assert t["next_sentence_label"].numel() == B
-            # ids / labels are range-clamped inside the kernels: no host synchronisation on the hot path
-        return t, B, T, Rv
-
-    def _engine_forward(self, tensors):
-        B, T = tensors["input_ids"].shape
-        Rv = tensors["image_feat"].shape[1]
-        eng = self._engine(B, T, Rv, self.training)
-        eng.arena.refresh_shadow()
-        if eng.fp8:
-            eng.arena.sync_optimizer()         # the re-quantisation reads the fp32 masters
-            eng.arena.refresh_fp8()
-        eng.bind_inputs(tensors)
-        if self._seed_base is None:
-            self.__dict__["_seed_base"] = int(torch.initial_seed())
-        eng.prepare_step(self._seed_base + self._step)
-        self.__dict__["_step"] += 1
-        eng.run_forward()
-        self.__dict__["_last"] = (eng, tensors)      # keeps the step's input tensors alive until backward
-        return getattr(eng, "losses", None)
+    def _losses(self, tensors):
+        losses = self._engine_forward(tensors)
+        return losses[0:1].clone(), losses[1:2].clone(), losses[2:3].clone()
 
     def _engine_backward(self, g_lm, g_img, g_nsp):
         eng, tensors = self._last
         state = self._backward_begin(eng)
         torch.cat([g_lm.reshape(1), g_img.reshape(1), g_nsp.reshape(1)], out=eng.gout)      # one launch, no temporary
         self._backward_run(eng, state)
-
-    def _backward_begin(self, eng, absent=()):
-        """Gradient-accumulation bookkeeping shared by the root models.  Parameters of torch-side head modules (`_torch_param_prefixes`) get
-        their gradients from autograd (redirected into the arena by a hook).  `absent`: arena names that receive no gradient in this
-        backward (a standalone BertModel's pooler whose output got none) -- left as they are, like `unused_params`."""
-        arena = eng.arena
-        from .optimization import flush_clip
-        flush_clip(arena)                   # a clip coefficient no optimizer step has consumed applies to the gradients it was computed for
-        skip = getattr(self, "_torch_param_prefixes", ())
-        # frozen parameters (requires_grad False: volta/train_utils.py:250-255) get no .grad, as under autograd; the
-        # optimizer and clip_grad_norm_ then leave their arena chunks alone
-        unused = eng.unused_params          # e.g. the VQA text pooler in pre-training: no launch reads it, .grad stays None
-        pairs = [((n, p), g) for (n, p), g in zip(arena.param_list(), arena.grad_views())
-                 if p.requires_grad and not (skip and n.startswith(skip)) and n not in unused and n not in absent]
-        params, gviews = [x[0] for x in pairs], [x[1] for x in pairs]
-        n_have = sum(p.grad is not None for _, p in params)
-        accumulate = n_have == len(params)
-        if n_have and not accumulate:
-            raise RuntimeError("volta_amd: some parameters carry a .grad and some do not; zero_grad() all of them")
-        old = None
-        if accumulate:
-            if not all(p.grad is g or p.grad.data_ptr() == g.data_ptr() for (_, p), g in zip(params, gviews)):
-                raise RuntimeError("volta_amd: .grad tensors were replaced by foreign tensors; call zero_grad(set_to_none=True)")
-            old = arena.grad.clone()
-        return params, gviews, accumulate, old
-
-    def _backward_run(self, eng, state):
-        params, gviews, accumulate, old = state
-        arena = eng.arena
-        skip = getattr(self, "_torch_param_prefixes", ())
-        if skip:            # the engine list zero-fills / overwrites only what it owns; torch-side head gradients are already in the arena
-            keep = [(g, g.clone()) for (n, _), g in zip(arena.param_list(), arena.grad_views()) if n.startswith(skip)] if accumulate else []
-        ddp = self.__dict__.get("_ddp")
-        if ddp is not None:
-            ddp.run_backward(eng)
-        else:
-            eng.bwd.run()
-        if accumulate:
-            from . import _lib as L
-            L.check(L.lib.vk_axpy_f32(L.ptr(arena.grad), L.ptr(old), 1.0, arena.total, L.stream_ptr()))
-            if skip:
-                for g, saved in keep:
-                    g.copy_(saved)
-        else:
-            for (_, p), g in zip(params, gviews):
-                p.grad = g
 
     # ------------------------------------------------------------------ public API
     def forward(self, input_ids, image_feat, image_loc, token_type_ids=None, attention_mask=None,
@@ -565,12 +593,7 @@ class BertForVLPreTraining(PreTrainedModel):
         tensors, B, T, Rv = self._prep_inputs(input_ids, image_feat, image_loc, token_type_ids, attention_mask,
                                               image_attention_mask, masked_lm_labels, image_label, image_cls, next_sentence_label,
                                               obj_labels, obj_confs, attr_labels, attr_confs)
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            self.materialize()
-            anchor = next(p for p in self.parameters() if p.requires_grad)
-            return _PretrainStep.apply(self, anchor, tensors)
-        losses = self._engine_forward(tensors)
-        return losses[0:1].clone(), losses[1:2].clone(), losses[2:3].clone()
+        return self._run_step(_PretrainStep, self._losses, tensors)
 
     def _scores(self, input_ids, image_feat, image_loc, token_type_ids, attention_mask, image_attention_mask, image_label, output_all_attention_masks=False):
         """The score-returning branch of BertForVLPreTraining.forward (volta/encoders.py:1065-1068,1113-1114): (prediction_scores_t [B,T,V],
@@ -632,50 +655,12 @@ class BertForVLPreTraining(PreTrainedModel):
                 itm = sc[:, :2]
             return scores_t, scores_v, itm, attn_maps, pooled
 
-    def encode(self, input_ids, image_feat, image_loc, token_type_ids=None, attention_mask=None, image_attention_mask=None,
-               output_all_encoded_layers=False, output_all_attention_masks=False):
-        """BertModel.forward: (seq_t [B,T,H], seq_v [B,Rv,H], pooled_t, pooled_v, attention maps = ([], [])); with
-        `output_all_encoded_layers` the two sequences are lists with both streams' states after EVERY sub-layer (encoders.py:868-881)."""
-        B, T = input_ids.shape
-        R = image_feat.shape[1] - self.add_global_imgfeat
-        dev = next(self.parameters()).device
-        dummy = dict(masked_lm_labels=torch.full((B, T), -1, dtype=torch.int64, device=dev),
-                     image_label=torch.full((B, R), -1, dtype=torch.int64, device=dev),
-                     image_cls=torch.zeros(B, R, 1601, device=dev), next_sentence_label=torch.zeros(B, dtype=torch.int64, device=dev),
-                     obj_labels=torch.zeros(B, R, dtype=torch.int64, device=dev), obj_confs=torch.zeros(B, R, device=dev),
-                     attr_labels=torch.zeros(B, R, dtype=torch.int64, device=dev), attr_confs=torch.zeros(B, R, device=dev))
-        tensors, B, T, Rv = self._prep_inputs(input_ids, image_feat, image_loc, token_type_ids, attention_mask, image_attention_mask, **dummy)
-        self.__dict__["_want_attn_maps"] = bool(output_all_attention_masks and self.config.visualization)
-        try:
-            with torch.no_grad():
-                self._engine_forward(tensors)
-        finally:
-            self.__dict__["_want_attn_maps"] = False
-        eng = self._last[0]
-        attn_maps = _attention_maps(self.config, eng, output_all_attention_masks)
-        H = self.config.hidden_size
-        pt, pv = eng.taps["pooled_t"], eng.taps["pooled_v"]          # None where the fusion method has no such pooler
-        Hv = self.config.v_hidden_size
-        if output_all_encoded_layers:
-            seq_t = [eng.taps["t%d" % n].view(B, T, H).float() for n in eng.sublayer_ids]
-            seq_v = [eng.taps["v%d" % n].view(B, Rv, Hv).float() for n in eng.sublayer_ids]
-        else:
-            seq_t, seq_v = eng.taps["seq_t"].view(B, T, H).float(), eng.taps["seq_v"].view(B, Rv, Hv).float()
-        return seq_t, seq_v, None if pt is None else pt.float(), None if pv is None else pv.float(), attn_maps
-
-
-# a standalone BertModel is a root model with the same engine plumbing (nested in a root model, `_root` routes everything to the root)
-for _name in ("set_dropout_seed", "_engine", "_prep_inputs", "_engine_forward", "_backward_begin", "_backward_run", "set_projection_dtype"):
-    setattr(BertModel, _name, getattr(BertForVLPreTraining, _name))
-
-
-def _bert_materialize(self, device=None):
-    root = self.__dict__.get("_root")
-    return root.materialize(device) if root is not None else BertForVLPreTraining.materialize(self, device)
-
-
-_bert_materialize.__doc__ = BertForVLPreTraining.materialize.__doc__
-BertModel.materialize = _bert_materialize
+    def _encode_labels(self, B, T, R, dev):
+        return dict(masked_lm_labels=torch.full((B, T), -1, dtype=torch.int64, device=dev),
+                    image_label=torch.full((B, R), -1, dtype=torch.int64, device=dev),
+                    image_cls=torch.zeros(B, R, 1601, device=dev), next_sentence_label=torch.zeros(B, dtype=torch.int64, device=dev),
+                    obj_labels=torch.zeros(B, R, dtype=torch.int64, device=dev), obj_confs=torch.zeros(B, R, device=dev),
+                    attr_labels=torch.zeros(B, R, dtype=torch.int64, device=dev), attr_confs=torch.zeros(B, R, device=dev))
 
 
 def _attention_maps(config, eng, requested):
@@ -707,12 +692,9 @@ class _TaskStep(torch.autograd.Function):
     re-enters it as the seed of the backward list."""
 
     @staticmethod
-    def forward(ctx, model, anchor, tensors):
-        model._engine_forward(tensors)
-        eng = model._last[0]
+    def forward(ctx, model, anchor, tensors, task_id, maps):
         ctx.model = model
-        C = eng.pred_shape[-1]
-        return eng.pred[:, :C].reshape(eng.pred_shape).clone()
+        return model._predict(tensors, task_id, maps)
 
     @staticmethod
     def backward(ctx, g_pred):
@@ -722,7 +704,7 @@ class _TaskStep(torch.autograd.Function):
         C = eng.pred_shape[-1]
         eng.d_pred[:, :C].copy_(g_pred.reshape(-1, C))        # the pad columns stay zero
         model._backward_run(eng, state)
-        return None, None, None
+        return None, None, None, None, None
 
 
 _TASK_LOSS_KINDS = {"bce_scaled": 0, "bce_mean": 1, "bce_regions": 2, "ce_options": 3}      # VK_TASK_* of include/volta_hip.h
@@ -752,11 +734,11 @@ def _task_loss_args(eng, tensors, target, kind, num_options):
             raise ValueError("kind 'ce_options' takes an int64 target of %d option indices" % groups)
     elif target.dtype != torch.float32 or target.numel() != groups * n:
         raise ValueError("kind %r takes a float32 target of %d x %d scores, got %s %r" % (kind, groups, n, target.dtype, tuple(target.shape)))
-    bufs = eng.__dict__.get("task_loss_bufs")
+    bufs = eng.task_loss_bufs
     if bufs is None or bufs[2].numel() != groups:
         dev = eng.pred.device
-        bufs = eng.__dict__["task_loss_bufs"] = (torch.empty(L.lib.vk_task_loss_work_bytes(groups), dtype=torch.uint8, device=dev),
-                                                 torch.empty(2, dtype=torch.float32, device=dev), torch.empty(groups, dtype=torch.int32, device=dev))
+        bufs = eng.task_loss_bufs = (torch.empty(L.lib.vk_task_loss_work_bytes(groups), dtype=torch.uint8, device=dev),
+                                     torch.empty(2, dtype=torch.float32, device=dev), torch.empty(groups, dtype=torch.int32, device=dev))
     work, out, amax = bufs
     return L.TaskLossArgs(L.ptr(eng.pred), L.ptr(target), L.ptr(mask), L.ptr(work), L.ptr(out), L.ptr(amax), code, groups, n, ld), out, amax
 
@@ -767,14 +749,9 @@ class _TaskLossStep(torch.autograd.Function):
     backward list.  Returns (float[2] = loss, score sum; int32 arg-max per group); only the loss carries a gradient."""
 
     @staticmethod
-    def forward(ctx, model, anchor, tensors, target, kind, num_options):
-        from . import _lib as L
-        model._engine_forward(tensors)
-        eng = model._last[0]
-        args, out, amax = _task_loss_args(eng, tensors, target, kind, num_options)
-        L.check(L.lib.vk_task_loss_fwd(args, L.stream_ptr()))
-        ctx.model, ctx.args, ctx.target = model, args, target       # the target stays alive until the backward has read it
-        res, idx = out.clone(), amax.clone()
+    def forward(ctx, model, anchor, tensors, task_id, target, kind, num_options):
+        ctx.model, ctx.target = model, target       # the target stays alive until the backward has read it
+        ctx.args, res, idx = model._task_loss_forward(tensors, task_id, target, kind, num_options)
         ctx.mark_non_differentiable(idx)
         return res, idx
 
@@ -787,32 +764,21 @@ class _TaskLossStep(torch.autograd.Function):
         g = g_res.to(torch.float32).contiguous()                    # g[0] = d(objective)/d(loss); the score carries none
         L.check(L.lib.vk_task_loss_bwd(ctx.args, L.ptr(g), L.ptr(eng.d_pred), L.stream_ptr()))
         model._backward_run(eng, state)
-        return None, None, None, None, None, None
+        return None, None, None, None, None, None, None
 
 
-class BertForVLTasks(PreTrainedModel):
+class BertForVLTasks(EngineHostModel):
     """Fine-tuning / evaluation model of the downstream tasks (volta/encoders.py:1117-1206): encoder, poolers, fusion + dropout and the
     task's classifier all run on the HIP engine, forward and backward; `clfs_dict` holds the classifiers' parameters under the reference's
     names and is never called."""
 
     _heads_mode = "tasks"
-    _torch_param_prefixes = ()
-    _vk_is_model = True
-    materialize = BertForVLPreTraining.materialize
-    _engine = BertForVLPreTraining._engine
-    _prep_inputs = BertForVLPreTraining._prep_inputs
-    _engine_forward = BertForVLPreTraining._engine_forward
-    _backward_begin = BertForVLPreTraining._backward_begin
-    _backward_run = BertForVLPreTraining._backward_run
-    set_dropout_seed = BertForVLPreTraining.set_dropout_seed
-    set_projection_dtype = BertForVLPreTraining.set_projection_dtype
 
     def __init__(self, config, task_cfg, task_ids, dropout_prob=0.1):
         super().__init__(config)
         self.bert = BertModel(config)
         if not 0.0 <= float(dropout_prob) < 1.0:
             raise ValueError("dropout probability has to be between 0 and 1, but got {}".format(dropout_prob))
-        self.__dict__["_task_dropout"] = float(dropout_prob)      # nn.Dropout(dropout_prob) of the reference (encoders.py:1122): an engine op here
         self.task_cfg = task_cfg
         task2clf = {}
         for task_id in task_ids:
@@ -844,42 +810,7 @@ class BertForVLTasks(PreTrainedModel):
             elif isinstance(mod, nn.LayerNorm):
                 mod.bias.data.zero_()
                 mod.weight.data.fill_(1.0)
-        self.add_global_imgfeat = int(config.add_global_imgfeat is not None)
-        self.__dict__["_arena"] = None
-        self.__dict__["_engines"] = {}
-        self.__dict__["_step"] = 0
-        self.__dict__["_seed_base"] = None
-        self.__dict__["_last"] = None
-        self.__dict__["_ddp"] = None
-        self.bert._adopt(self)
-        for mod in self.modules():
-            if mod is not self and isinstance(mod, PreTrainedModel):
-                mod.__dict__["_root"] = self
-        for n, p in self.named_parameters():
-            p._vk_owner = self
-
-    def encode(self, input_ids, image_feat, image_loc, token_type_ids=None, attention_mask=None, image_attention_mask=None,
-               output_all_encoded_layers=False, output_all_attention_masks=False):
-        """BertModel.forward under no_grad (BertModel.forward delegates here)."""
-        tensors, B, T, Rv = self._prep_inputs(input_ids, image_feat, image_loc, token_type_ids, attention_mask, image_attention_mask,
-                                              None, None, None, None)
-        self.__dict__["_want_attn_maps"] = bool(output_all_attention_masks and self.config.visualization)
-        try:
-            with torch.no_grad():
-                self._engine_forward(tensors)
-        finally:
-            self.__dict__["_want_attn_maps"] = False
-        eng = self._last[0]
-        attn_maps = _attention_maps(self.config, eng, output_all_attention_masks)
-        H = self.config.hidden_size
-        pt, pv = eng.taps["pooled_t"], eng.taps["pooled_v"]          # None where the fusion method has no such pooler
-        Hv = self.config.v_hidden_size
-        if output_all_encoded_layers:
-            seq_t = [eng.taps["t%d" % n].view(B, T, H).float() for n in eng.sublayer_ids]
-            seq_v = [eng.taps["v%d" % n].view(B, Rv, Hv).float() for n in eng.sublayer_ids]
-        else:
-            seq_t, seq_v = eng.taps["seq_t"].view(B, T, H).float(), eng.taps["seq_v"].view(B, Rv, Hv).float()
-        return seq_t, seq_v, None if pt is None else pt.float(), None if pv is None else pv.float(), attn_maps
+        self._init_root_state(task_dropout=dropout_prob)      # nn.Dropout(dropout_prob) of the reference (encoders.py:1122): an engine op here
 
     def task_loss(self, input_txt, input_imgs, image_loc, task_id, token_type_ids=None, attention_mask=None, image_attention_mask=None,
                   target=None, *, kind, num_options=None):
@@ -900,49 +831,33 @@ class BertForVLTasks(PreTrainedModel):
             raise ValueError("kind %r (%s)" % (kind, " | ".join(_TASK_LOSS_KINDS)))
         if target is None:
             raise ValueError("task_loss needs the target")
-        tensors, B, T, Rv = self._prep_inputs(input_txt, input_imgs, image_loc, token_type_ids, attention_mask, image_attention_mask,
-                                              None, None, None, None)
+        tensors, B, T, Rv = self._prep_inputs(input_txt, input_imgs, image_loc, token_type_ids, attention_mask, image_attention_mask)
         dev = tensors["input_ids"].device
         target = target.to(device=dev).contiguous()
-        self.__dict__["_cur_task"] = task_id
-        try:
-            self.materialize()
-            if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-                anchor = next(p for p in self.parameters() if p.requires_grad)
-                res, idx = _TaskLossStep.apply(self, anchor, tensors, target, kind, num_options)
-            else:
-                from . import _lib as L
-                with torch.no_grad():
-                    self._engine_forward(tensors)
-                    args, out, amax = _task_loss_args(self._last[0], tensors, target, kind, num_options)
-                    L.check(L.lib.vk_task_loss_fwd(args, L.stream_ptr()))
-                    res, idx = out.clone(), amax.clone()
-        finally:
-            self.__dict__["_cur_task"] = None
-        return res, idx
+        return self._run_step(_TaskLossStep, lambda *a: self._task_loss_forward(*a)[1:], tensors, task_id, target, kind, num_options)
+
+    def _task_loss_forward(self, tensors, task_id, target, kind, num_options):
+        """The forward list of `task_id`'s plan, then vk_task_loss_fwd on its logits: (the launch's arguments, float[2], int32 arg-max)."""
+        from . import _lib as L
+        self._engine_forward(tensors, task_id)
+        args, out, amax = _task_loss_args(self._last[0], tensors, target, kind, num_options)
+        L.check(L.lib.vk_task_loss_fwd(args, L.stream_ptr()))
+        return args, out.clone(), amax.clone()
+
+    def _predict(self, tensors, task_id, maps):
+        """The forward list of `task_id`'s plan (the plan whose head is this task's classifier): its logits in fp32."""
+        self._engine_forward(tensors, task_id, maps)
+        eng = self._last[0]
+        C = eng.pred_shape[-1]
+        return eng.pred[:, :C].reshape(eng.pred_shape).clone()
 
     def forward(self, input_txt, input_imgs, image_loc, task_id, token_type_ids=None, attention_mask=None,
                 image_attention_mask=None, output_all_encoded_layers=False, output_all_attention_masks=False):
         if task_id not in self.task_cfg or task_id not in self.clfs_dict:
             raise KeyError("unknown task id %r" % (task_id,))
-        tensors, B, T, Rv = self._prep_inputs(input_txt, input_imgs, image_loc, token_type_ids, attention_mask, image_attention_mask,
-                                              None, None, None, None)
-        self.__dict__["_cur_task"] = task_id                    # selects the plan whose head is this task's classifier
-        self.__dict__["_want_attn_maps"] = bool(output_all_attention_masks and self.config.visualization)
-        try:
-            self.materialize()
-            if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-                anchor = next(p for p in self.parameters() if p.requires_grad)
-                vil_prediction = _TaskStep.apply(self, anchor, tensors)
-            else:
-                with torch.no_grad():
-                    self._engine_forward(tensors)
-                eng = self._last[0]
-                C = eng.pred_shape[-1]
-                vil_prediction = eng.pred[:, :C].reshape(eng.pred_shape).clone()
-        finally:
-            self.__dict__["_cur_task"] = None
-            self.__dict__["_want_attn_maps"] = False
+        tensors, B, T, Rv = self._prep_inputs(input_txt, input_imgs, image_loc, token_type_ids, attention_mask, image_attention_mask)
+        maps = bool(output_all_attention_masks and self.config.visualization)
+        vil_prediction = self._run_step(_TaskStep, self._predict, tensors, task_id, maps)
         attn_maps = _attention_maps(self.config, self._last[0], output_all_attention_masks)
         if self.task_cfg[task_id]["type"].startswith("V-logit"):   # padded regions are masked out of the region scores (encoders.py:1198-1199)
             mask = tensors["image_attention_mask"].to(vil_prediction.dtype)
