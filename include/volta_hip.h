@@ -784,6 +784,31 @@ typedef struct vk_task_batch_args {
 } vk_task_batch_args;
 int vk_task_batch(const vk_task_batch_args* a, vk_stream_t s);
 
+/* Retrieval ranks (eval_retrieval.py:200-263 without a sort).  One total order defines every output: the key of (score s, index j) is
+ * sortable(s) << 32 | (0xFFFFFFFF - j), sortable: fp32 -> uint32 monotone, -0.0 == +0.0, every NaN lowest; a larger key ranks earlier, which
+ * is the position in np.argsort(-s, kind="stable").
+ *   rank_ir[c]  images whose key in row c exceeds the key of caption c's own image; -1 when caption_image[c] is outside [0, Ni) (S is not read)
+ *   topk_ir[c]  the K images with the largest keys of row c, in order; -1 past Ni
+ *   rank_tr[i]  minimum over the captions c of image i of the number of captions c' with key (S[c', i], c') above (S[c, i], c); -1 without one
+ * The captions of an image come as a CSR over the captions with a valid image: image_ptr [Ni + 1], image_captions [>= image_ptr[Ni]].
+ * `target_key` [Nc] and `count` [Nc] are workspace (count is cleared by the call).  Three launches and one memset on `s`; integer counts and
+ * integer atomics only, so the result is deterministic. */
+#define VK_RANKS_MAX_TOPK 64
+typedef struct vk_retrieval_ranks_args {
+    const float* S;                  /* [Nc, Ni], row stride ld >= Ni */
+    const int32_t* caption_image;    /* [Nc] */
+    const int32_t* image_ptr;        /* [Ni + 1] */
+    const int32_t* image_captions;   /* [Nc] */
+    int32_t* rank_ir;                /* [Nc] */
+    int32_t* topk_ir;                /* [Nc, K]; may be NULL when K == 0 */
+    int32_t* rank_tr;                /* [Ni] */
+    uint32_t* target_key;            /* [Nc] workspace */
+    int32_t* count;                  /* [Nc] workspace */
+    int64_t ld;
+    int32_t Nc, Ni, K, reserved_;
+} vk_retrieval_ranks_args;
+int vk_retrieval_ranks(const vk_retrieval_ranks_args* a, vk_stream_t s);
+
 /* ------------------------------------------------------------------------------------------------
  * Record readers in front of the batch producer.  Host code (no stream argument): files are memory-mapped and fields
  * are decoded straight into the caller's staging slot -- use pinned memory and one cudaMemcpyAsync per batch.

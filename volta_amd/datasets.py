@@ -6,6 +6,8 @@ on the device.
   NLVR2Dataset               volta/datasets/nlvr2_dataset.py      two images packed into one block of 2 * max_region_num rows
   ReferExpressionDataset     volta/datasets/refer_expression_dataset.py   one image, IoU target [R, 1] against the referred box
   RetrievalDataset           volta/datasets/retrieval_dataset.py:45-257   four options: true pair, random caption, random image, hard caption
+  RetrievalDatasetVal        volta/datasets/retrieval_dataset.py:260-417  the test set: every caption against every image; `device_arrays`
+  RetrievalEvalMap / RetrievalEvalLoader                                  its map and the driver's batch-of-one loader over resident arrays
   DatasetMapTrain / Eval     volta/datasets/__init__.py           task name -> class; any other name raises a KeyError naming the reference class
   TaskLoader                 torch's DataLoader + default_collate + `.cuda()` of the drivers, as staging -> one copy -> `vk_task_batch`
 
@@ -471,6 +473,179 @@ class RetrievalDataset(_TaskDataset):
                 torch.from_numpy(np.stack([mask1, mask1, mask3, mask1])), tok, 0, im, seg, ids[0])
 
 
+class RetrievalDatasetVal(_TaskDataset):
+    """volta/datasets/retrieval_dataset.py:260-417, the retrieval test set: every caption against every image.
+
+    Annotations as `_load_annotationsVal`: the image id is `id` (RetrievalCOCO) or the stem of `img_path` (RetrievalFlickr30k), images in
+    first-seen order, one caption entry per sentence.  Tokenisation as :340-375 through `_tokenize`.  `caption_image[c]` is the index of
+    caption c's image in the image list; a caption whose image is not in the list is refused here with a ValueError that names it (the
+    reference fails in the driver with an IndexError).
+
+    Host surface (the compatibility surface; never used by the fast path): `len` is 2 * captions and `dataset[index]` is the reference's
+    9-tuple for caption index // 2 against the image half index % 2 -- (features_all, spatials_all, image_mask_all) of images [:500] or
+    [500:], caption, input_mask, segment_ids, target_all float32 [500], caption_idx, image_idx -- from host copies of the image arrays
+    built on first use through the reader.  The `[:500]` / `[500:]` halves and the length-500 target are kept as they are: with more than
+    1000 images a target past 500 raises the reference's IndexError.
+
+    Device surface: `device_arrays(device)` -> dict of `features` [Ni, R, F] fp32, `spatials` [Ni, R, num_locs] fp32, `image_mask` [Ni, R]
+    int64, `input_ids` / `input_mask` / `segment_ids` [Nc, T] int64, `caption_image` [Nc] int32, `image_ids` [Ni] int64, resident on the
+    device (the reference keeps a float64 host copy of everything).  The image arrays are assembled by `vk_task_batch` writing into slices
+    of the resident arrays, from chunks of at most `chunk_images` images that `ImageStager` decodes into two alternating pinned staging
+    sets: same kernel as the other datasets, so the values equal the reference's bit for bit."""
+
+    target_kind = "zero"
+    HALF = 500                      # the reference's image block (retrieval_dataset.py:382-392, eval_retrieval.py:184)
+
+    def __init__(self, *args, chunk_images=256, **kw):
+        kw.setdefault("max_seq_length", 20)
+        kw.setdefault("max_region_num", 36)
+        super().__init__(*args, **kw)
+        self.num_labels = 1
+        self.chunk_images = max(1, min(256, int(chunk_images)))
+        path = args[2] if len(args) > 2 else kw["annotations_jsonpath"]
+        images, self._caption_entries = {}, []
+        for ann in _read_jsonlines(path):
+            if self.task == "RetrievalCOCO":
+                image_id = ann["id"]
+            elif self.task == "RetrievalFlickr30k":
+                image_id = int(ann["img_path"].split(".")[0])
+            else:
+                raise ValueError("RetrievalDatasetVal serves RetrievalCOCO and RetrievalFlickr30k, not %r" % self.task)
+            images[image_id] = 1
+            for sent in ann["sentences"]:
+                self._caption_entries.append(dict(caption=sent, image_id=image_id))
+        self._image_entries = [*images]
+        self.entries = self._caption_entries
+        self.caption_image = self._index_captions(self._image_entries, self._caption_entries)
+        self._text = self._tokenize([e["caption"] for e in self._caption_entries])
+        self._host, self._device = None, {}
+
+    @staticmethod
+    def _index_captions(image_entries, caption_entries):
+        """int32 [captions]: the position of each caption's image in `image_entries`"""
+        at = {image_id: i for i, image_id in enumerate(image_entries)}
+        out = np.empty(len(caption_entries), np.int32)
+        for c, e in enumerate(caption_entries):
+            if e["image_id"] not in at:
+                raise ValueError("caption %d (%r) belongs to image %r, which is not among the %d images of the set" % (c, e["caption"], e["image_id"], len(at)))
+            out[c] = at[e["image_id"]]
+        return out
+
+    def __len__(self):
+        return 2 * len(self._caption_entries)
+
+    def host_tables(self):
+        """the small tables `device_arrays` uploads, as numpy"""
+        return dict(input_ids=self._text[0], input_mask=self._text[1], segment_ids=self._text[2], caption_image=self.caption_image,
+                    image_ids=np.asarray(self._image_entries, np.int64))
+
+    def _host_arrays(self):
+        if self._host is None:
+            blocks = []
+            for image_id in self._image_entries:
+                features, _, boxes, _ = self._image_features_reader[image_id]
+                blocks.append(self._pad_block([(features, boxes)]))
+            F = blocks[0][0].shape[1] if blocks else int(self._image_features_reader.feature_size)
+            R = self.block_rows
+            self._host = tuple(torch.from_numpy(np.stack([b[k] for b in blocks]) if blocks else np.zeros(shape, dt))
+                               for k, (shape, dt) in enumerate((((0, R, F), np.float32), ((0, R, self._num_locs), np.float32), ((0, R), np.int64))))
+        return self._host
+
+    def _target_pos(self, caption_idx, half):
+        """(position of the caption's image in the image half, or None)"""
+        pos = int(self.caption_image[caption_idx]) - half * self.HALF
+        if pos < 0 or (half == 0 and pos >= self.HALF):
+            return None
+        if pos >= self.HALF:        # target_all[i] = 1 with i past the 500 entries (retrieval_dataset.py:399-402)
+            raise IndexError("index %d is out of bounds for dimension 0 with size %d" % (pos, self.HALF))
+        return pos
+
+    def __getitem__(self, index):
+        caption_idx, image_idx = int(index / 2), index % 2
+        half = slice(0, self.HALF) if image_idx == 0 else slice(self.HALF, None)
+        features, spatials, image_mask = (t[half] for t in self._host_arrays())
+        tok, im, seg = (torch.from_numpy(t[caption_idx]) for t in self._text)
+        target_all = torch.zeros(self.HALF)
+        pos = self._target_pos(caption_idx, image_idx)
+        if pos is not None:
+            target_all[pos] = 1
+        return features, spatials, image_mask, tok, im, seg, target_all, caption_idx, image_idx
+
+    def device_arrays(self, device="cuda"):
+        device = torch.device(device)
+        if device.type != "cuda" or not torch.cuda.is_available():
+            raise RuntimeError("RetrievalDatasetVal.device_arrays assembles the image arrays with vk_task_batch on an MI355X; there is no host "
+                               "path (index the dataset for that)")
+        if device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        if device not in self._device:
+            self._device[device] = self._assemble(device)
+        return self._device[device]
+
+    def _chunk_blocks(self, n):
+        """n [S]: region counts of a staged chunk -> (segs int32 [S, TASK_MAX_SEGS, 4], mask counts int32 [S]) for `vk_task_batch`: image s
+        fills block s from its logical row 0, masked up to min(rows, block length)"""
+        S, R = len(n), self.block_rows
+        segs = np.zeros((S, L.TASK_MAX_SEGS, 4), np.int32)
+        segs[:, 0, 0], segs[:, 0, 3] = np.arange(S), R
+        return segs, np.minimum(np.asarray(n, np.int64) + int(self._add_global_imgfeat is not None), R).astype(np.int32)
+
+    def _assemble(self, dev):
+        from . import ops
+        Ni, R = len(self._image_entries), self.block_rows
+        stager = ImageStager(self._image_features_reader, sets=2)
+        out = dict(features=torch.empty(Ni, R, stager.F, dtype=torch.float32, device=dev),
+                   spatials=torch.empty(Ni, R, self._num_locs, dtype=torch.float32, device=dev),
+                   image_mask=torch.empty(Ni, R, dtype=torch.int64, device=dev))
+        with torch.cuda.device(dev):
+            busy = [None, None]                 # per staging set: the event after which its pinned memory may be rewritten
+            for k, i0 in enumerate(range(0, Ni, self.chunk_images)):
+                which = k % 2
+                if busy[which] is not None:
+                    busy[which].synchronize()
+                h = stager.stage(self._image_entries[i0:i0 + self.chunk_images], which)
+                S = h["S"]
+                feat, boxes = (h["stage"][name][:S].to(dev, non_blocking=True) for name in ("feat", "boxes"))
+                segs, counts = self._chunk_blocks(h["n"])
+                small = torch.from_numpy(np.concatenate([h["n"], h["wh"].reshape(-1), counts, segs.reshape(-1)]).astype(np.int32))
+                small = (small.pin_memory() if stager._pin else small).to(dev, non_blocking=True)      # the small tables as one copy
+                ops.task_batch(feat, boxes, small[:S], small[S:3 * S].view(S, 2), small[4 * S:].view(S, L.TASK_MAX_SEGS, 4), small[3 * S:4 * S], R,
+                               self._num_locs, self._add_global_imgfeat, out={name: t[i0:i0 + S] for name, t in out.items()})
+                busy[which] = torch.cuda.Event()
+                busy[which].record()
+            for name, table in self.host_tables().items():
+                out[name] = torch.from_numpy(np.ascontiguousarray(table)).to(dev)
+            torch.cuda.current_stream().synchronize()      # the staging sets go away with the stager
+        return out
+
+
+class RetrievalEvalLoader:
+    """What the driver's DataLoader(batch_size=1) over a RetrievalDatasetVal yields (eval_retrieval.py:168-170), as device tensors: per index
+    the collated 9-tuple with its leading dimension of 1.  The image tensors are views of the dataset's resident arrays (no copy), so the
+    unchanged driver loop runs -- slowly, through the whole model; `volta_amd.retrieval.evaluate_retrieval` is the fast path."""
+
+    def __init__(self, dataset, device="cuda"):
+        self.dataset, self.device, self.batch_size = dataset, device, 1
+
+    def __len__(self):
+        return len(self.dataset)
+
+    def __iter__(self):
+        ds = self.dataset
+        arr = ds.device_arrays(self.device)
+        dev, H = arr["features"].device, ds.HALF
+        for index in range(len(ds)):
+            c, half = index // 2, index % 2
+            lo, hi = (0, H) if half == 0 else (H, None)
+            target = torch.zeros(1, H, dtype=torch.float32, device=dev)
+            pos = ds._target_pos(c, half)
+            if pos is not None:
+                target[0, pos] = 1
+            yield (arr["features"][lo:hi].unsqueeze(0), arr["spatials"][lo:hi].unsqueeze(0), arr["image_mask"][lo:hi].unsqueeze(0),
+                   arr["input_ids"][c:c + 1], arr["input_mask"][c:c + 1], arr["segment_ids"][c:c + 1], target,
+                   torch.full((1,), c, dtype=torch.int64, device=dev), torch.full((1,), half, dtype=torch.int64, device=dev))
+
+
 class _DatasetMap(dict):
     """task name -> dataset class; a task this module does not cover names the reference class to fall back to"""
 
@@ -487,7 +662,8 @@ class _DatasetMap(dict):
 _COMMON = {"VQA": VQAClassificationDataset, "GQA": GQAClassificationDataset, "NLVR2": NLVR2Dataset, "refcoco": ReferExpressionDataset,
            "refcoco+": ReferExpressionDataset, "refcocog": ReferExpressionDataset}
 DatasetMapTrain = _DatasetMap(_COMMON, RetrievalCOCO=RetrievalDataset, RetrievalFlickr30k=RetrievalDataset)
-DatasetMapEval = _DatasetMap(_COMMON)      # retrieval evaluation: RetrievalScorer takes the feature arrays directly (volta_amd/retrieval.py)
+DatasetMapEval = _DatasetMap(_COMMON)      # the datasets TaskLoader batches; retrieval evaluation is not one of them:
+RetrievalEvalMap = {"RetrievalCOCO": RetrievalDatasetVal, "RetrievalFlickr30k": RetrievalDatasetVal}    # LoadDatasetEval consults this first
 
 
 # ------------------------------------------------------------------------------------------------ samplers

@@ -253,3 +253,38 @@ def task_batch(feat, boxes, n, wh, segs, mask_count, R, num_locs, add_global, sc
     check(L.lib.vk_task_batch(C.byref(a), stream_ptr()))
     a._refs = (feat, boxes, n, wh, segs, mask_count, mean, scatter, ref_box)
     return out
+
+
+def retrieval_ranks(S, caption_image, topk=20):
+    """vk_retrieval_ranks (csrc/ranks.hip): S fp32 [Nc, Ni] on the GPU (rows `S.stride(0) >= Ni` apart: a column slice of a wider tensor is
+    taken as it is), caption_image int32 [Nc] = the index of each caption's image -> (rank_ir int32 [Nc], topk_ir int32 [Nc, topk],
+    rank_tr int32 [Ni]), all on the device, no host synchronisation.
+
+    One total order defines all three: element (score s, index j) has the key sortable(s) << 32 | (0xFFFFFFFF - j), where sortable maps
+    fp32 to uint32 monotonically, -0.0 and +0.0 alike and every NaN lowest; a larger key ranks earlier.  That is the position in
+    np.argsort(-s, kind="stable") (NaN last).  rank_ir[c]: images ranked before caption c's own in row c, -1 when caption_image[c] is outside
+    [0, Ni); topk_ir[c]: the first `topk` (0..64) images of row c, -1 past Ni; rank_tr[i]: the best position, in column i, of a caption of
+    image i, -1 when it has none.  The reference driver calls np.argsort(-s) without `kind`, which is not stable: its rank is only defined
+    where the target's score is untied in its row / column, and on those inputs the two agree."""
+    assert S.is_cuda and S.dtype == torch.float32 and S.dim() == 2 and S.shape[0] > 0 and S.shape[1] > 0, "S: a non-empty fp32 [Nc, Ni] cuda tensor"
+    Nc, Ni = S.shape
+    assert S.stride(1) == 1 or Ni == 1, "the scores of a row must be adjacent"
+    ld = S.stride(0) if Nc > 1 else max(S.stride(0), Ni)
+    have = S.untyped_storage().nbytes() // 4 - S.storage_offset()
+    assert ld >= Ni and (Nc - 1) * ld + Ni <= have, "S does not cover %d rows of %d scores %d apart" % (Nc, Ni, ld)
+    assert caption_image.is_cuda and caption_image.dtype == torch.int32 and tuple(caption_image.shape) == (Nc,) and caption_image.is_contiguous()
+    K, dev = int(topk), S.device
+    # the captions of each image as a CSR over the captions with a valid image (sort + counts; nothing here reads a value on the host)
+    ci = caption_image.long()
+    bucket = torch.where((ci >= 0) & (ci < Ni), ci, torch.full_like(ci, Ni))
+    image_captions = torch.sort(bucket, stable=True)[1].int()
+    counts = torch.zeros(Ni + 1, dtype=torch.int64, device=dev).index_add_(0, bucket, torch.ones_like(bucket))
+    image_ptr = torch.zeros(Ni + 1, dtype=torch.int32, device=dev)
+    image_ptr[1:] = torch.cumsum(counts[:Ni], 0)
+    rank_ir, rank_tr = torch.empty(Nc, dtype=torch.int32, device=dev), torch.empty(Ni, dtype=torch.int32, device=dev)
+    topk_ir = torch.empty(Nc, max(K, 0), dtype=torch.int32, device=dev)
+    work = torch.empty(2, Nc, dtype=torch.int32, device=dev)
+    a = L.RetrievalRanksArgs(ptr(S), ptr(caption_image), ptr(image_ptr), ptr(image_captions), ptr(rank_ir), ptr(topk_ir) if K > 0 else None, ptr(rank_tr),
+                             ptr(work[0]), ptr(work[1]), ld, Nc, Ni, K, 0)
+    check(L.lib.vk_retrieval_ranks(C.byref(a), stream_ptr()))
+    return rank_ir, topk_ir, rank_tr

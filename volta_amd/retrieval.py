@@ -17,9 +17,14 @@ Scores: a BertForVLTasks with a VL-logit task gives its raw logit (eval_retrieva
 softmax(seq_relationship_score)[:, 0] (eval_retrieval.py:181-185).  The scorer leaves the model's state alone: `training`, the dropout step
 counter, the model's last forward and its engines; it reads the current weights (the bf16 copies are refreshed as the model's forward
 refreshes them).  Handles hold prefix outputs computed with the weights of the time they were encoded.
+
+`evaluate_retrieval(model, dset_val, task_id)` is the whole of eval_retrieval.py:161-263 on top of it: the device arrays of a
+`volta_amd.datasets.RetrievalDatasetVal`, the score matrix, `ops.retrieval_ranks` (csrc/ranks.hip: ranks and top-k by counting keys, no sort)
+and one transfer of the integer ranks; the recall / rank numbers are the driver's own float64 arithmetic on that copy.
 """
 import ctypes as C
 
+import numpy as np
 import torch
 
 from .modules import sublayer_schedule
@@ -260,3 +265,49 @@ class RetrievalScorer:
                 s = torch.empty_like(s).index_copy_(0, order, s)
                 Lg = torch.empty_like(Lg).index_copy_(0, order, Lg) if Lg is not None else None
         return (s, Lg) if return_logits else s
+
+
+def rank_metrics(ranks):
+    """eval_retrieval.py:225-230 / 258-263 on a vector of 0-based ranks, in float64 numpy as the driver computes them."""
+    r = np.asarray(ranks, dtype=np.float64)
+    return dict(r1=100.0 * np.sum(r < 1) / len(r), r5=100.0 * np.sum(r < 5) / len(r), r10=100.0 * np.sum(r < 10) / len(r),
+                medr=np.floor(np.median(r) + 1), meanr=np.mean(r) + 1)
+
+
+class RetrievalResult:
+    """image_retrieval / text_retrieval: dicts of r1, r5, r10, medr, meanr; results: per caption the top-k image indices (what the driver
+    dumps into *_result.json); rank_ir [Nc], rank_tr [Ni] int32 and score_matrix [Nc, Ni] fp32 stay on the device."""
+
+    def __init__(self, image_retrieval, text_retrieval, results, rank_ir, rank_tr, score_matrix):
+        self.image_retrieval, self.text_retrieval, self.results = image_retrieval, text_retrieval, results
+        self.rank_ir, self.rank_tr, self.score_matrix = rank_ir, rank_tr, score_matrix
+
+
+def evaluate_retrieval(model, dset_val, task_id=None, pair_chunk=1000, topk=20):
+    """eval_retrieval.py:161-263 for a `RetrievalDatasetVal`: image retrieval (per caption, the rank of its image) and text retrieval (per
+    image, the best rank of one of its captions) as recall@1/5/10, median and mean rank, plus the top-`topk` images per caption.
+
+    `model`: a BertForVLTasks with the VL-logit task `task_id`, or a BertForVLPreTraining with task_id None (zero-shot), bare or wrapped in
+    volta_amd.parallel.DistributedDataParallel; what RetrievalScorer refuses is refused here with its messages, and the model's state is
+    left alone as the scorer leaves it.  Any number of captions and images (COCO's 5k test set is the same call).
+
+    Ties: ranks follow np.argsort(-s, kind="stable") with NaN last (ops.retrieval_ranks).  The driver's np.argsort(-s) is not stable, so
+    its rank is only defined where the target's score is untied; there the two agree.  Images without a caption are left out of the
+    text-retrieval statistics (the driver's `min(ranks)` fails on them)."""
+    from . import ops
+    from .parallel import DistributedDataParallel
+    if isinstance(model, DistributedDataParallel):
+        model = model.module
+    scorer = RetrievalScorer(model, task_id, pair_chunk=pair_chunk)
+    if not 0 <= int(topk) <= 64:
+        raise ValueError("topk must be in 0..64, got %r" % (topk,))
+    arr = dset_val.device_arrays(scorer.device)
+    caps = scorer.encode_captions(arr["input_ids"], arr["segment_ids"], arr["input_mask"])
+    imgs = scorer.encode_images(arr["features"], arr["spatials"], arr["image_mask"])
+    S = scorer.score_matrix(caps, imgs)
+    rank_ir, topk_ir, rank_tr = ops.retrieval_ranks(S, arr["caption_image"], int(topk))
+    Nc, Ni, K = rank_ir.numel(), rank_tr.numel(), int(topk)
+    host = torch.cat([rank_ir, rank_tr, topk_ir.reshape(-1)]).cpu().numpy()          # the one transfer
+    ir, tr, top = host[:Nc], host[Nc:Nc + Ni], host[Nc + Ni:].reshape(Nc, K)
+    results = [[int(v) for v in row if v >= 0] for row in top]
+    return RetrievalResult(rank_metrics(ir), rank_metrics(tr[tr >= 0]), results, rank_ir, rank_tr, S)

@@ -10,7 +10,7 @@ VOLTA_TASK_LOSS=torch forces that path (the A/B switch of tools/bench_task_step.
 
 LoadDataset / LoadDatasetEval (volta/task_utils.py:290-426) build the datasets of volta_amd.datasets over this project's readers and hand out
 `TaskLoader`s, which assemble the batches on the device (csrc/taskbatch.hip); VQA, GQA, NLVR2, refcoco / refcoco+ / refcocog and (training)
-RetrievalCOCO / RetrievalFlickr30k are covered, any other task name raises a KeyError that names the reference class to fall back to."""
+RetrievalCOCO / RetrievalFlickr30k are covered, LoadDatasetEval also serves the retrieval test sets (RetrievalDatasetVal), any other task name raises a KeyError that names the reference class to fall back to."""
 import os
 
 import torch
@@ -103,7 +103,9 @@ def LoadDataset(args, config, task_cfg, task_id, split="trainval"):
 
 
 def LoadDatasetEval(args, config, task_cfg, task_id):
-    """-> (batch_size, task2num_iters, dset_val, dl_val): `eval_batch_size` of the task (else args.batch_size), args.split over the task's val_split"""
+    """-> (batch_size, task2num_iters, dset_val, dl_val): `eval_batch_size` of the task (else args.batch_size), args.split over the task's val_split.
+    RetrievalCOCO / RetrievalFlickr30k (datasets.RetrievalEvalMap): a RetrievalDatasetVal, {task: 2 * captions} and a RetrievalEvalLoader, what
+    eval_retrieval.py:131 expects; `volta_amd.retrieval.evaluate_retrieval(model, dset_val, ...)` then replaces the driver's loop."""
     from . import datasets as D
     tokenizer = _tokenizer(args)
     task = "TASK" + task_id
@@ -113,7 +115,12 @@ def LoadDatasetEval(args, config, task_cfg, task_id):
     world = _world(args)[0]
     if args.local_rank != -1:
         batch_size = int(batch_size / world)
-    dset_val = _dataset(D.DatasetMapEval, args, config, cfg, readers, tokenizer, cfg["val_annotations_jsonpath"], args.split if args.split else cfg["val_split"])
+    split = args.split if args.split else cfg["val_split"]
+    if cfg["name"] in D.RetrievalEvalMap:
+        dset_val = _dataset(D.RetrievalEvalMap, args, config, cfg, readers, tokenizer, cfg["val_annotations_jsonpath"], split)
+        dl_val = D.RetrievalEvalLoader(dset_val)
+        return batch_size, {task: len(dl_val)}, dset_val, dl_val
+    dset_val = _dataset(D.DatasetMapEval, args, config, cfg, readers, tokenizer, cfg["val_annotations_jsonpath"], split)
     dl_val = D.TaskLoader(dset_val, batch_size, None, drop_last=args.drop_last, in_memory=args.in_memory, threads=_threads(args, world))
     return batch_size, {task: len(dl_val)}, dset_val, dl_val
 
