@@ -809,6 +809,40 @@ typedef struct vk_retrieval_ranks_args {
 } vk_retrieval_ranks_args;
 int vk_retrieval_ranks(const vk_retrieval_ranks_args* a, vk_stream_t s);
 
+/* Hard-negative pool of the retrieval task (csrc/knn.hip; volta_amd/retrieval.py generate_hard_pool).
+ *
+ * vk_image_means: mean[s][f] = (((feat[s][0][f] + feat[s][1][f]) + ...) + feat[s][n[s] - 1][f]) / n[s] in fp32, each operation rounded on its
+ * own: np.sum(features, 0) / n bit for bit.  feat / n are what the image stager leaves ([S, Rcap, F], rows >= n[s] are not read); n[s] is
+ * cut to [0, Rcap], n[s] == 0 gives NaN. */
+typedef struct vk_image_means_args {
+    const float* feat;               /* [S, Rcap, F] */
+    const int32_t* n;                /* [S] */
+    float* mean;                     /* [S, F] */
+    int32_t S, Rcap, F, reserved_;
+} vk_image_means_args;
+int vk_image_means(const vk_image_means_args* a, vk_stream_t s);
+
+/* vk_knn_pool: X fp32 [N, D], contiguous and finite -> out int32 [N, k]: row i holds the first k candidates j (j = i included) under the
+ * total order (d2(i, j) ascending, then j ascending), d2(i, j) = sum_k (double(x_ik) - double(x_jk))^2 accumulated in float64 in one fixed
+ * order, so equal vectors are at equal distance and the index decides.  The answer is exact for every finite input: an fp32-MFMA screen
+ * keeps M candidates per row (k <= M <= min(N, VK_KNN_MAX_SHORTLIST)), a float64 pass orders them and certifies the row with a rigorous
+ * bound on the screen's error, and the rows it cannot certify are recomputed in float64 against all N candidates.  stats[0] / stats[1]
+ * count the certified / recomputed rows (stats[0] + stats[1] == N).  `work`: vk_knn_pool_work_bytes(N, D, k, M) bytes, 256-byte aligned
+ * (-1 for a shape the call would refuse).  Everything runs on `s`; nothing is read back by the host.  VK_KNN_SCREEN_ONLY stops after the
+ * screen (timing: `out` and `stats[0..1]` stay unwritten apart from the cleared counters). */
+#define VK_KNN_MAX_SHORTLIST 256
+#define VK_KNN_SCREEN_ONLY 1
+typedef struct vk_knn_pool_args {
+    const float* X;                  /* [N, D] */
+    int32_t* out;                    /* [N, k] */
+    void* work;
+    int32_t* stats;                  /* [2]: certified rows, recomputed rows */
+    int64_t work_bytes;
+    int32_t N, D, k, M, flags, reserved_;
+} vk_knn_pool_args;
+int64_t vk_knn_pool_work_bytes(int N, int D, int k, int M);
+int vk_knn_pool(const vk_knn_pool_args* a, vk_stream_t s);
+
 /* ------------------------------------------------------------------------------------------------
  * Record readers in front of the batch producer.  Host code (no stream argument): files are memory-mapped and fields
  * are decoded straight into the caller's staging slot -- use pinned memory and one cudaMemcpyAsync per batch.

@@ -288,3 +288,63 @@ def retrieval_ranks(S, caption_image, topk=20):
                              ptr(work[0]), ptr(work[1]), ld, Nc, Ni, K, 0)
     check(L.lib.vk_retrieval_ranks(C.byref(a), stream_ptr()))
     return rank_ir, topk_ir, rank_tr
+
+
+def image_means(feat, n):
+    """vk_image_means (csrc/knn.hip): feat fp32 [S, Rcap, F] and n int32 [S] on the GPU, as `ImageStager.stage()` leaves them (rows >= n[s]
+    are not read) -> mean fp32 [S, F] = np.sum(feat[s, :n[s]], 0) / n[s] bit for bit (rows added in order in fp32, then one division)."""
+    assert feat.dtype == torch.float32 and feat.dim() == 3 and feat.is_contiguous() and feat.shape[1] > 0 and feat.shape[2] > 0, "feat: a contiguous fp32 [S, Rcap, F] tensor"
+    S, Rcap, F = feat.shape
+    assert n.dtype == torch.int32 and tuple(n.shape) == (S,) and n.is_contiguous(), "n: a contiguous int32 [S] tensor"
+    assert feat.is_cuda and n.is_cuda, "feat and n must be cuda tensors"
+    mean = torch.empty(S, F, dtype=torch.float32, device=feat.device)
+    a = L.ImageMeansArgs(ptr(feat), ptr(n), ptr(mean), S, Rcap, F, 0)
+    check(L.lib.vk_image_means(C.byref(a), stream_ptr()))
+    return mean
+
+
+def knn_default_shortlist(k):
+    """the screen's shortlist for k neighbours: k plus a margin of 28 % (128 for k = 100), at most VK_KNN_MAX_SHORTLIST"""
+    return min(L.KNN_MAX_SHORTLIST, max(k, -(-k * 32 // 25)))
+
+
+def knn_pool(X, k, shortlist=None, return_stats=False, screen_only=False):
+    """vk_knn_pool (csrc/knn.hip): X fp32 [N, D] on the GPU, contiguous and finite -> int32 [N, k], row i = the first k indices j under the
+    total order (d2(i, j), j) with d2 the float64 squared Euclidean distance; j = i is a candidate like any other (it comes first unless an
+    equal vector has a lower index).  Exact for every finite input: an fp32-MFMA screen keeps `shortlist` candidates per
+    row (default knn_default_shortlist(k), cut to N), float64 orders and certifies them, uncertified rows are recomputed in float64.
+    `return_stats=True` also returns dict(certified=..., fallback=...), the row counts of the two paths (one host read).  `screen_only`
+    runs the screen alone (timing): the returned tensor is then not written."""
+    assert X.dtype == torch.float32, "X: fp32 expected, got %s" % X.dtype
+    assert X.dim() == 2 and X.shape[0] > 0 and X.shape[1] > 0, "X: a non-empty [N, D] matrix expected, got shape %s" % (tuple(X.shape),)
+    assert X.is_contiguous(), "X must be contiguous"
+    N, D = X.shape
+    k = int(k)
+    if k < 1:
+        raise ValueError("k = %d: at least one neighbour" % k)
+    if k > N:
+        raise ValueError("k = %d neighbours of N = %d vectors: k must be less than or equal to the number of vectors" % (k, N))
+    if k > L.KNN_MAX_SHORTLIST:
+        raise ValueError("k = %d exceeds the shortlist limit of %d" % (k, L.KNN_MAX_SHORTLIST))
+    M = knn_default_shortlist(k) if shortlist is None else int(shortlist)
+    if shortlist is not None and not k <= M <= L.KNN_MAX_SHORTLIST:
+        raise ValueError("shortlist = %d: expected k = %d <= shortlist <= %d" % (M, k, L.KNN_MAX_SHORTLIST))
+    M = min(M, N)
+    assert X.is_cuda, "X must be a cuda tensor"
+    if not bool(torch.isfinite(X).all()):
+        raise ValueError("X holds non-finite values")
+    nbytes = L.lib.vk_knn_pool_work_bytes(N, D, k, M)
+    if nbytes < 0:
+        raise L.VoltaHipError(L.lib.vk_last_error().decode())
+    dev = X.device
+    work = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
+    work = work[(-work.data_ptr()) % 256:]
+    out = torch.empty(N, k, dtype=torch.int32, device=dev)
+    stats = torch.empty(2, dtype=torch.int32, device=dev)
+    a = L.KnnPoolArgs(ptr(X), ptr(out), ptr(work), ptr(stats), nbytes, N, D, k, M, L.KNN_SCREEN_ONLY if screen_only else 0, 0)
+    check(L.lib.vk_knn_pool(C.byref(a), stream_ptr()))
+    work.record_stream(torch.cuda.current_stream())
+    if return_stats:
+        c, f = stats.tolist()
+        return out, dict(certified=c, fallback=f)
+    return out

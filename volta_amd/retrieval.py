@@ -311,3 +311,76 @@ def evaluate_retrieval(model, dset_val, task_id=None, pair_chunk=1000, topk=20):
     ir, tr, top = host[:Nc], host[Nc:Nc + Ni], host[Nc + Ni:].reshape(Nc, K)
     results = [[int(v) for v in row if v >= 0] for row in top]
     return RetrievalResult(rank_metrics(ir), rank_metrics(tr[tr >= 0]), results, rank_ir, rank_tr, S)
+
+
+# ------------------------------------------------------------------------------------------------ the hard-negative pool of the training set
+def train_image_list(annotations_jsonpath, task):
+    """The image id of every annotation line, in file order: `int(img_path.split(".")[0])` for RetrievalFlickr30k (scripts/generate_pool.py:35-39),
+    `id` for RetrievalCOCO (the rule of `RetrievalDataset`)."""
+    from .datasets import _read_jsonlines
+    if task not in ("RetrievalFlickr30k", "RetrievalCOCO"):
+        raise ValueError("task: RetrievalFlickr30k or RetrievalCOCO expected, not %r" % (task,))
+    anns = _read_jsonlines(annotations_jsonpath)
+    return [int(ann["img_path"].split(".")[0]) if task == "RetrievalFlickr30k" else ann["id"] for ann in anns]
+
+
+def image_mean_features(features_reader, image_list, chunk=256, device="cuda"):
+    """fp32 [len(image_list), F] on the device: per image the mean of its region features, `np.sum(features, 0) / num_boxes` bit for bit --
+    row 0 of what an `ImageFeaturesH5Reader` with a leading global feature returns.  `chunk` images are decoded by one `ImageStager.stage`
+    call, copied once and reduced by `ops.image_means`."""
+    from . import ops
+    from .datasets import ImageStager
+    chunk = int(chunk)
+    if chunk < 1:
+        raise ValueError("chunk = %d: at least one image per chunk" % chunk)
+    stager = ImageStager(features_reader, sets=1)
+    means = torch.empty(len(image_list), stager.F, dtype=torch.float32, device=device)
+    for i0 in range(0, len(image_list), chunk):
+        ids = image_list[i0:i0 + chunk]
+        order = list(dict.fromkeys(ids))                                 # the stager takes distinct ids
+        h = stager.stage(order)
+        if int(h["n"].min()) < 1:
+            raise ValueError("image %r has no region" % (order[int(h["n"].argmin())],))
+        S = h["S"]
+        if h["staged_all"]:
+            feat = h["stage"]["feat"][:S].to(device)
+        else:
+            feat = torch.zeros(S, h["Rcap"], stager.F, dtype=torch.float32)
+            for s, (f, _) in enumerate(h["src"]):
+                feat[s, :f.shape[0]] = f
+            feat = feat.to(device)
+        m = ops.image_means(feat.contiguous(), torch.from_numpy(h["n"]).to(device))
+        if len(order) != len(ids):
+            slot = {iid: s for s, iid in enumerate(order)}
+            m = m[torch.as_tensor([slot[iid] for iid in ids], device=device)]
+        means[i0:i0 + len(ids)] = m
+    return means
+
+
+def generate_hard_pool(features_reader, annotations_jsonpath, task, k=100, out=None, chunk=256):
+    """`hard_negative.pkl` of `RetrievalDataset(split="train")`, the product of the reference's scripts/generate_pool.py: per training image
+    (one per annotation line) the k nearest training images under the Euclidean distance, in float64, between mean region features.
+
+    Returns dict(train_hard_pool=float64 ndarray [N, k] of positions in train_image_list, train_image_list=list of int) -- dtype and layout
+    of what the script pickles.  Row i is ordered by (distance, position): the image itself is a candidate like any other, as in the script's
+    `BallTree.query`, and comes first unless an image with the same mean feature has a lower position.  The search is exact (`ops.knn_pool`).
+    `out`: a path to pickle the result to, or True for `<directory of the annotations>/hard_negative.pkl`; None writes nothing."""
+    from . import ops
+    import os
+    import pickle
+    k = int(k)
+    if k < 1:
+        raise ValueError("k = %d: at least one neighbour" % k)
+    image_list = train_image_list(annotations_jsonpath, task)
+    if k > len(image_list):
+        raise ValueError("k = %d neighbours of %d training images: k must be less than or equal to the number of images" % (k, len(image_list)))
+    if out is not None and out is not True and not isinstance(out, (str, bytes, os.PathLike)):
+        raise ValueError("out: a path, True or None expected, not %r" % (out,))
+    means = image_mean_features(features_reader, image_list, chunk)
+    pool = ops.knn_pool(means, k).cpu().numpy().astype(np.float64)
+    result = dict(train_hard_pool=pool, train_image_list=image_list)
+    if out is not None:
+        path = os.path.join(os.path.dirname(os.path.abspath(annotations_jsonpath)), "hard_negative.pkl") if out is True else out
+        with open(path, "wb") as f:
+            pickle.dump(result, f)
+    return result
