@@ -809,6 +809,37 @@ typedef struct vk_retrieval_ranks_args {
 } vk_retrieval_ranks_args;
 int vk_retrieval_ranks(const vk_retrieval_ranks_args* a, vk_stream_t s);
 
+/* The same ranks with the captions sharded: a shard owns the contiguous captions [row0, row0 + nrows) of Nc and holds their scores,
+ * S [nrows, Ni] with row stride ld.  Every other array is global-sized and globally indexed (caption_image, the CSR, the outputs).
+ *   vk_retrieval_ranks_shard_rows  writes rank_ir[row0 + r], topk_ir[row0 + r, :K] and target_key[row0 + r] for the local rows r (one launch;
+ *                                  positions of other shards are not touched).  Reads S, caption_image.
+ *   vk_retrieval_ranks_shard_cols  target_key must now hold every shard's words.  For each CSR entry e (caption c of image i) adds to count[e]
+ *                                  the number of local rows r with sortable(S[r, i]) above target_key[c], or equal to it with row0 + r < c.
+ *                                  Clears count first (one memset) unless flags has VK_RANKS_ACCUMULATE (several local blocks on one
+ *                                  device).  Reads S, the CSR, target_key.  One launch.
+ *   vk_retrieval_ranks_finish      rank_tr[i] = minimum of count over the entries of image i, -1 without one; count is the SUM of all shards'
+ *                                  count arrays.  Reads image_ptr, count.  One launch.
+ * Counts are integers, so the sum of the shards' arrays, in any order, is the unsharded array bit for bit, and the three calls over all
+ * shards give the outputs of vk_retrieval_ranks.  nrows == 0 is legal: no launch (shard_cols still clears count when asked to).  Each call
+ * reads only the members named for it; the others may be NULL. */
+#define VK_RANKS_ACCUMULATE 1
+typedef struct vk_retrieval_ranks_shard_args {
+    const float* S;                  /* [nrows, Ni], row stride ld >= Ni; may be NULL when nrows == 0 */
+    const int32_t* caption_image;    /* [Nc] */
+    const int32_t* image_ptr;        /* [Ni + 1] */
+    const int32_t* image_captions;   /* [Nc] */
+    int32_t* rank_ir;                /* [Nc] */
+    int32_t* topk_ir;                /* [Nc, K]; may be NULL when K == 0 */
+    int32_t* rank_tr;                /* [Ni] */
+    uint32_t* target_key;            /* [Nc] */
+    int32_t* count;                  /* [Nc] */
+    int64_t ld;
+    int32_t Nc, Ni, K, row0, nrows, flags;
+} vk_retrieval_ranks_shard_args;
+int vk_retrieval_ranks_shard_rows(const vk_retrieval_ranks_shard_args* a, vk_stream_t s);
+int vk_retrieval_ranks_shard_cols(const vk_retrieval_ranks_shard_args* a, vk_stream_t s);
+int vk_retrieval_ranks_finish(const vk_retrieval_ranks_shard_args* a, vk_stream_t s);
+
 /* Hard-negative pool of the retrieval task (csrc/knn.hip; volta_amd/retrieval.py generate_hard_pool).
  *
  * vk_image_means: mean[s][f] = (((feat[s][0][f] + feat[s][1][f]) + ...) + feat[s][n[s] - 1][f]) / n[s] in fp32, each operation rounded on its

@@ -185,6 +185,14 @@ class RetrievalRanksArgs(C.Structure):
                [("ld", C.c_int64)] + [(n, i32) for n in ("Nc", "Ni", "K", "reserved_")]
 
 
+RANKS_ACCUMULATE = 1       # VK_RANKS_ACCUMULATE
+
+
+class RetrievalRanksShardArgs(C.Structure):
+    _fields_ = [(n, c_p) for n in ("S", "caption_image", "image_ptr", "image_captions", "rank_ir", "topk_ir", "rank_tr", "target_key", "count")] + \
+               [("ld", C.c_int64)] + [(n, i32) for n in ("Nc", "Ni", "K", "row0", "nrows", "flags")]
+
+
 KNN_MAX_SHORTLIST, KNN_SCREEN_ONLY = 256, 1      # VK_KNN_MAX_SHORTLIST, VK_KNN_SCREEN_ONLY
 
 
@@ -324,6 +332,9 @@ _sig("vk_grad_sqnorm_list_work_floats", C.c_int)
 _sig("vk_grad_seed", C.c_int, C.POINTER(GradSeedArgs), c_p)
 _sig("vk_pair_gather", C.c_int, C.POINTER(PairGatherArgs), c_p)
 _sig("vk_retrieval_ranks", C.c_int, C.POINTER(RetrievalRanksArgs), c_p)
+_sig("vk_retrieval_ranks_shard_rows", C.c_int, C.POINTER(RetrievalRanksShardArgs), c_p)
+_sig("vk_retrieval_ranks_shard_cols", C.c_int, C.POINTER(RetrievalRanksShardArgs), c_p)
+_sig("vk_retrieval_ranks_finish", C.c_int, C.POINTER(RetrievalRanksShardArgs), c_p)
 _sig("vk_image_means", C.c_int, C.POINTER(ImageMeansArgs), c_p)
 _sig("vk_knn_pool_work_bytes", C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int)
 _sig("vk_knn_pool", C.c_int, C.POINTER(KnnPoolArgs), c_p)
@@ -365,7 +376,7 @@ EXPORTS = ["vk_version", "vk_device_arch", "vk_last_error", "vk_set_seed", "vk_c
            "vk_axpy_f32", "vk_sum_slabs_f32", "vk_sum_slabs_bf16", "vk_memset_async", "vk_hold_cus", "vk_gate_wait", "vk_bump_u64", "vk_store_u64", "vk_gate_value", "vk_comm_standin", "vk_gemm_reserve_cus", "vk_side_tail", "vk_run_ops", "vk_run_ops_timed", "vk_side_join", "vk_side_join_from", "vk_side_stream", "vk_side_enable", "vk_concap_batch",
            "vk_lmdb_open", "vk_lmdb_close", "vk_lmdb_entries", "vk_lmdb_first", "vk_lmdb_next", "vk_lmdb_get", "vk_concap_record_decode", "vk_concap_records_decode", "vk_b64_decode",
            "vk_wordpiece_open", "vk_wordpiece_close", "vk_wordpiece_vocab_size", "vk_wordpiece_token_id", "vk_wordpiece_encode", "vk_wordpiece_encode_batch",
-           "vk_task_batch", "vk_task_images_stage", "vk_retrieval_ranks", "vk_image_means", "vk_knn_pool_work_bytes", "vk_knn_pool"]
+           "vk_task_batch", "vk_task_images_stage", "vk_retrieval_ranks", "vk_retrieval_ranks_shard_rows", "vk_retrieval_ranks_shard_cols", "vk_retrieval_ranks_finish", "vk_image_means", "vk_knn_pool_work_bytes", "vk_knn_pool"]
 
 
 def check(rc):

@@ -14,6 +14,11 @@
 //                      COL_CHUNK targets; per-wave counts meet in LDS and leave as one integer atomicAdd per (target, workgroup).
 //   ranks_min_kernel   per image the minimum of its captions' counts, -1 without a caption.
 // Counts and minima are integers: the result does not depend on the order in which workgroups finish.
+//
+// Sharded over captions (vk_retrieval_ranks_shard_rows / _shard_cols / _finish): a shard holds the rows [row0, row0 + nrows) of the matrix.
+// The row pass is row-local and writes at the rows' global positions; the column pass counts the shard's rows against the targets of ALL
+// captions, with the global row index row0 + r in the tie rule, so the shards' count arrays add up to the unsharded one bit for bit
+// (integers, any order); the minimum is taken over the sum.  Both kernels are the unsharded ones instantiated with SHARD = true.
 #include "common.h"
 #include "../../include/volta_hip.h"
 #include "util.h"
@@ -68,12 +73,21 @@ __device__ __forceinline__ void row_foreach(const float* __restrict__ row, int n
     if (t < n - done) f(done + t, row[done + t]);
 }
 
-__global__ __launch_bounds__(RANK_THREADS) void ranks_row_kernel(const vk_retrieval_ranks_args a, const int resident) {
+// what the three kernels read: vk_retrieval_ranks_args, and for a shard the rows [row0, row0 + nrows) that S holds
+struct ranks_params {
+    vk_retrieval_ranks_args a;
+    int32_t row0, nrows;
+};
+
+// SHARD: S holds the rows [row0, row0 + nrows) only; outputs and caption_image are indexed by the global row
+template <bool SHARD>
+__global__ __launch_bounds__(RANK_THREADS) void ranks_row_kernel(const ranks_params p, const int resident) {
+    const vk_retrieval_ranks_args& a = p.a;
     extern __shared__ __attribute__((aligned(16))) uint32_t row_keys[];       // [Ni] when resident
     __shared__ uint64_t best_slot[2][RANK_THREADS / 64];
     __shared__ int count_slot[RANK_THREADS / 64];
-    const int c = blockIdx.x, t = threadIdx.x, lane = t & 63, w = t >> 6, Ni = a.Ni;
-    const float* __restrict__ row = a.S + (int64_t)c * a.ld;
+    const int c = (SHARD ? p.row0 : 0) + (int)blockIdx.x, t = threadIdx.x, lane = t & 63, w = t >> 6, Ni = a.Ni;
+    const float* __restrict__ row = a.S + (int64_t)blockIdx.x * a.ld;
     const int tj = a.caption_image[c];
     const bool valid = (uint32_t)tj < (uint32_t)Ni;                            // the guarded read: an image index outside the row reads nothing
     const uint32_t tsk = valid ? sortable(row[tj]) : 0u;
@@ -115,12 +129,16 @@ __global__ __launch_bounds__(RANK_THREADS) void ranks_row_kernel(const vk_retrie
     }
 }
 
-__global__ __launch_bounds__(RANK_THREADS) void ranks_col_kernel(const vk_retrieval_ranks_args a) {
+// SHARD: the rows r of S are the captions row0 + r; targets are all Nc captions, the tie rule compares global caption indices
+template <bool SHARD>
+__global__ __launch_bounds__(RANK_THREADS) void ranks_col_kernel(const ranks_params p) {
+    const vk_retrieval_ranks_args& a = p.a;
     __shared__ int part[RANK_THREADS / 64][COL_CHUNK][COL_BLOCK];
     const int t = threadIdx.x, lane = t & 63, w = t >> 6, Nc = a.Nc, Ni = a.Ni;
     const int col0 = blockIdx.x * COL_BLOCK, col = col0 + lane;
     const bool live = col < Ni;
-    const int r0 = blockIdx.y * COL_ROWS, r1 = min(Nc, r0 + COL_ROWS);
+    const int row0 = SHARD ? p.row0 : 0;
+    const int r0 = blockIdx.y * COL_ROWS, r1 = min(SHARD ? p.nrows : Nc, r0 + COL_ROWS);
     const int e0 = live ? min(max(a.image_ptr[col], 0), Nc) : 0, e1 = live ? min(max(a.image_ptr[col + 1], 0), Nc) : 0;
     int most = e1 - e0;                                                        // lane -> column is the same in all four waves, so is this maximum
 #pragma unroll
@@ -142,7 +160,7 @@ __global__ __launch_bounds__(RANK_THREADS) void ranks_col_kernel(const vk_retrie
         for (int r = r0 + w; r < r1; r += RANK_THREADS / 64) {
             const uint32_t sk = live ? sortable(src[(int64_t)r * a.ld]) : 0u;
 #pragma unroll
-            for (int k = 0; k < COL_CHUNK; ++k) above[k] += (int)((sk > tk[k]) | ((sk == tk[k]) & ((uint32_t)r < tc[k])));
+            for (int k = 0; k < COL_CHUNK; ++k) above[k] += (int)((sk > tk[k]) | ((sk == tk[k]) & ((uint32_t)(row0 + r) < tc[k])));
         }
 #pragma unroll
         for (int k = 0; k < COL_CHUNK; ++k) part[w][k][lane] = above[k];
@@ -159,7 +177,8 @@ __global__ __launch_bounds__(RANK_THREADS) void ranks_col_kernel(const vk_retrie
     }
 }
 
-__global__ __launch_bounds__(RANK_THREADS) void ranks_min_kernel(const vk_retrieval_ranks_args a) {
+__global__ __launch_bounds__(RANK_THREADS) void ranks_min_kernel(const ranks_params p) {
+    const vk_retrieval_ranks_args& a = p.a;
     const int i = blockIdx.x * RANK_THREADS + threadIdx.x;
     if (i >= a.Ni) return;
     const int e0 = min(max(a.image_ptr[i], 0), a.Nc), e1 = min(max(a.image_ptr[i + 1], 0), a.Nc);
@@ -189,10 +208,66 @@ extern "C" int vk_retrieval_ranks(const vk_retrieval_ranks_args* a, vk_stream_t 
     if (hipMemsetAsync(a->count, 0, sizeof(int32_t) * (size_t)a->Nc, st) != hipSuccess) return set_error("vk_retrieval_ranks: clearing the counts failed");
     const int resident = a->Ni <= RANK_RESIDENT;
     const size_t lds = resident ? (((size_t)a->Ni * 4 + 15) & ~(size_t)15) : 0;
-    hipLaunchKernelGGL(ranks_row_kernel, dim3((unsigned)a->Nc), dim3(RANK_THREADS), lds, st, *a, resident);
+    const ranks_params p{*a, 0, a->Nc};
+    hipLaunchKernelGGL(ranks_row_kernel<false>, dim3((unsigned)a->Nc), dim3(RANK_THREADS), lds, st, p, resident);
     if (check_launch("vk_retrieval_ranks (rows)")) return -1;
-    hipLaunchKernelGGL(ranks_col_kernel, dim3(cb, rb), dim3(RANK_THREADS), 0, st, *a);
+    hipLaunchKernelGGL(ranks_col_kernel<false>, dim3(cb, rb), dim3(RANK_THREADS), 0, st, p);
     if (check_launch("vk_retrieval_ranks (columns)")) return -1;
-    hipLaunchKernelGGL(ranks_min_kernel, dim3((unsigned)((a->Ni + RANK_THREADS - 1) / RANK_THREADS)), dim3(RANK_THREADS), 0, st, *a);
+    hipLaunchKernelGGL(ranks_min_kernel, dim3((unsigned)((a->Ni + RANK_THREADS - 1) / RANK_THREADS)), dim3(RANK_THREADS), 0, st, p);
     return check_launch("vk_retrieval_ranks (minima)");
+}
+
+// what the three shard calls check alike; `what` names the call
+static int shard_check(const vk_retrieval_ranks_shard_args* a, const char* what) {
+    if (!a) return set_error("%s: null argument struct", what);
+    if (a->Nc <= 0 || a->Ni <= 0) return set_error("%s: %d captions x %d images; both must be positive", what, a->Nc, a->Ni);
+    if (a->row0 < 0 || a->nrows < 0 || (int64_t)a->row0 + a->nrows > a->Nc)
+        return set_error("%s: rows [%d, %lld) are not inside the %d captions", what, a->row0, (long long)a->row0 + a->nrows, a->Nc);
+    if (a->ld < a->Ni) return set_error("%s: leading dimension %lld is shorter than a row of %d scores", what, (long long)a->ld, a->Ni);
+    if ((uintptr_t)a->S & 3) return set_error("%s: S is not 4-byte aligned", what);
+    return 0;
+}
+
+static ranks_params shard_params(const vk_retrieval_ranks_shard_args* a) {
+    ranks_params p{};
+    p.a.S = a->S, p.a.caption_image = a->caption_image, p.a.image_ptr = a->image_ptr, p.a.image_captions = a->image_captions;
+    p.a.rank_ir = a->rank_ir, p.a.topk_ir = a->topk_ir, p.a.rank_tr = a->rank_tr, p.a.target_key = a->target_key, p.a.count = a->count;
+    p.a.ld = a->ld, p.a.Nc = a->Nc, p.a.Ni = a->Ni, p.a.K = a->K;
+    p.row0 = a->row0, p.nrows = a->nrows;
+    return p;
+}
+
+extern "C" int vk_retrieval_ranks_shard_rows(const vk_retrieval_ranks_shard_args* a, vk_stream_t s) {
+    if (shard_check(a, "vk_retrieval_ranks_shard_rows")) return -1;
+    if (a->K < 0 || a->K > VK_RANKS_MAX_TOPK) return set_error("vk_retrieval_ranks_shard_rows: top-k of %d, expected 0..%d", a->K, VK_RANKS_MAX_TOPK);
+    if ((a->nrows > 0 && !a->S) || !a->caption_image || !a->rank_ir || !a->target_key || (a->K > 0 && !a->topk_ir))
+        return set_error("vk_retrieval_ranks_shard_rows: null pointer (S, caption_image, rank_ir, target_key%s)", a->K > 0 ? ", topk_ir" : "");
+    if (a->nrows == 0) return 0;                                               // an empty shard: nothing to write
+    const int resident = a->Ni <= RANK_RESIDENT;
+    const size_t lds = resident ? (((size_t)a->Ni * 4 + 15) & ~(size_t)15) : 0;
+    hipLaunchKernelGGL(ranks_row_kernel<true>, dim3((unsigned)a->nrows), dim3(RANK_THREADS), lds, (hipStream_t)s, shard_params(a), resident);
+    return check_launch("vk_retrieval_ranks_shard_rows");
+}
+
+extern "C" int vk_retrieval_ranks_shard_cols(const vk_retrieval_ranks_shard_args* a, vk_stream_t s) {
+    if (shard_check(a, "vk_retrieval_ranks_shard_cols")) return -1;
+    if (a->flags & ~VK_RANKS_ACCUMULATE) return set_error("vk_retrieval_ranks_shard_cols: unknown flags 0x%x", (unsigned)a->flags);
+    if ((a->nrows > 0 && !a->S) || !a->image_ptr || !a->image_captions || !a->target_key || !a->count)
+        return set_error("vk_retrieval_ranks_shard_cols: null pointer (S, image_ptr, image_captions, target_key, count)");
+    const unsigned cb = (unsigned)((a->Ni + COL_BLOCK - 1) / COL_BLOCK), rb = (unsigned)((a->nrows + COL_ROWS - 1) / COL_ROWS);
+    if (rb > 65535u) return set_error("vk_retrieval_ranks_shard_cols: %d rows exceed the column pass's %d row blocks of %d", a->nrows, 65535, COL_ROWS);
+    hipStream_t st = (hipStream_t)s;
+    if (!(a->flags & VK_RANKS_ACCUMULATE) && hipMemsetAsync(a->count, 0, sizeof(int32_t) * (size_t)a->Nc, st) != hipSuccess)
+        return set_error("vk_retrieval_ranks_shard_cols: clearing the counts failed");
+    if (a->nrows == 0) return 0;                                               // an empty shard counts nothing
+    hipLaunchKernelGGL(ranks_col_kernel<true>, dim3(cb, rb), dim3(RANK_THREADS), 0, st, shard_params(a));
+    return check_launch("vk_retrieval_ranks_shard_cols");
+}
+
+extern "C" int vk_retrieval_ranks_finish(const vk_retrieval_ranks_shard_args* a, vk_stream_t s) {
+    if (!a) return set_error("vk_retrieval_ranks_finish: null argument struct");
+    if (a->Nc <= 0 || a->Ni <= 0) return set_error("vk_retrieval_ranks_finish: %d captions x %d images; both must be positive", a->Nc, a->Ni);
+    if (!a->image_ptr || !a->count || !a->rank_tr) return set_error("vk_retrieval_ranks_finish: null pointer (image_ptr, count, rank_tr)");
+    hipLaunchKernelGGL(ranks_min_kernel, dim3((unsigned)((a->Ni + RANK_THREADS - 1) / RANK_THREADS)), dim3(RANK_THREADS), 0, (hipStream_t)s, shard_params(a));
+    return check_launch("vk_retrieval_ranks_finish");
 }

@@ -255,6 +255,19 @@ def task_batch(feat, boxes, n, wh, segs, mask_count, R, num_locs, add_global, sc
     return out
 
 
+def _ranks_csr(caption_image, Ni):
+    """the captions of each image as a CSR over the captions with a valid image (sort + counts; nothing here reads a value on the host)
+    -> image_ptr int32 [Ni + 1], image_captions int32 [Nc]"""
+    dev = caption_image.device
+    ci = caption_image.long()
+    bucket = torch.where((ci >= 0) & (ci < Ni), ci, torch.full_like(ci, Ni))
+    image_captions = torch.sort(bucket, stable=True)[1].int()
+    counts = torch.zeros(Ni + 1, dtype=torch.int64, device=dev).index_add_(0, bucket, torch.ones_like(bucket))
+    image_ptr = torch.zeros(Ni + 1, dtype=torch.int32, device=dev)
+    image_ptr[1:] = torch.cumsum(counts[:Ni], 0)
+    return image_ptr, image_captions
+
+
 def retrieval_ranks(S, caption_image, topk=20):
     """vk_retrieval_ranks (csrc/ranks.hip): S fp32 [Nc, Ni] on the GPU (rows `S.stride(0) >= Ni` apart: a column slice of a wider tensor is
     taken as it is), caption_image int32 [Nc] = the index of each caption's image -> (rank_ir int32 [Nc], topk_ir int32 [Nc, topk],
@@ -274,13 +287,7 @@ def retrieval_ranks(S, caption_image, topk=20):
     assert ld >= Ni and (Nc - 1) * ld + Ni <= have, "S does not cover %d rows of %d scores %d apart" % (Nc, Ni, ld)
     assert caption_image.is_cuda and caption_image.dtype == torch.int32 and tuple(caption_image.shape) == (Nc,) and caption_image.is_contiguous()
     K, dev = int(topk), S.device
-    # the captions of each image as a CSR over the captions with a valid image (sort + counts; nothing here reads a value on the host)
-    ci = caption_image.long()
-    bucket = torch.where((ci >= 0) & (ci < Ni), ci, torch.full_like(ci, Ni))
-    image_captions = torch.sort(bucket, stable=True)[1].int()
-    counts = torch.zeros(Ni + 1, dtype=torch.int64, device=dev).index_add_(0, bucket, torch.ones_like(bucket))
-    image_ptr = torch.zeros(Ni + 1, dtype=torch.int32, device=dev)
-    image_ptr[1:] = torch.cumsum(counts[:Ni], 0)
+    image_ptr, image_captions = _ranks_csr(caption_image, Ni)
     rank_ir, rank_tr = torch.empty(Nc, dtype=torch.int32, device=dev), torch.empty(Ni, dtype=torch.int32, device=dev)
     topk_ir = torch.empty(Nc, max(K, 0), dtype=torch.int32, device=dev)
     work = torch.empty(2, Nc, dtype=torch.int32, device=dev)
@@ -288,6 +295,82 @@ def retrieval_ranks(S, caption_image, topk=20):
                              ptr(work[0]), ptr(work[1]), ld, Nc, Ni, K, 0)
     check(L.lib.vk_retrieval_ranks(C.byref(a), stream_ptr()))
     return rank_ir, topk_ir, rank_tr
+
+
+class RanksShard:
+    """What `retrieval_ranks_shard` leaves for the rest of the sharded sequence.  rank_ir int32 [Nc], topk_ir int32 [Nc, K] and target_key
+    int32 [Nc] (the bits of the kernel's uint32 words) are global-sized: written at the shard's rows [row0, row0 + nrows), zero elsewhere, so
+    the element-wise integer SUM over all shards is the whole array.  image_ptr / image_captions: the global CSR."""
+
+    def __init__(self, S, ld, row0, nrows, Nc, Ni, K, rank_ir, topk_ir, target_key, image_ptr, image_captions):
+        self.S, self.ld, self.row0, self.nrows, self.Nc, self.Ni, self.K = S, ld, row0, nrows, Nc, Ni, K
+        self.rank_ir, self.topk_ir, self.target_key, self.image_ptr, self.image_captions = rank_ir, topk_ir, target_key, image_ptr, image_captions
+
+    def args(self, **kw):
+        a = L.RetrievalRanksShardArgs(S=ptr(self.S) if self.nrows else None, image_ptr=ptr(self.image_ptr), image_captions=ptr(self.image_captions),
+                                      ld=self.ld, Nc=self.Nc, Ni=self.Ni, K=self.K, row0=self.row0, nrows=self.nrows)
+        for k, v in kw.items():
+            setattr(a, k, v)
+        return a
+
+
+def retrieval_ranks_shard(S_local, row0, Nc, caption_image, topk=20):
+    """vk_retrieval_ranks_shard_rows (csrc/ranks.hip): the row pass of `retrieval_ranks` for the shard that owns the captions
+    [row0, row0 + nrows) of Nc.  S_local fp32 [nrows, Ni] on the GPU (rows `stride(0) >= Ni` apart; nrows may be 0), caption_image int32 [Nc]
+    = the GLOBAL table -> a `RanksShard`.  One launch (none for an empty shard) after the CSR build, no host synchronisation.
+
+    The sequence, with `+` an integer sum over the shards (an all_reduce, or a plain add when one device holds several):
+        sh = retrieval_ranks_shard(S_local, row0, Nc, caption_image, topk)
+        count = retrieval_ranks_shard_counts(sh, + sh.target_key)
+        rank_tr = retrieval_ranks_finish(+ count, sh.image_ptr, Ni);   rank_ir = + sh.rank_ir;   topk_ir = + sh.topk_ir
+    gives the three outputs of `retrieval_ranks` on the whole matrix, bit for bit."""
+    assert S_local.is_cuda and S_local.dtype == torch.float32 and S_local.dim() == 2 and S_local.shape[1] > 0, "S_local: an fp32 [nrows, Ni] cuda tensor"
+    nrows, Ni = S_local.shape
+    row0, Nc, K, dev = int(row0), int(Nc), int(topk), S_local.device
+    assert Nc > 0 and 0 <= row0 and row0 + nrows <= Nc, "rows [%d, %d) are not inside the %d captions" % (row0, row0 + nrows, Nc)
+    ld = Ni
+    if nrows:
+        assert S_local.stride(1) == 1 or Ni == 1, "the scores of a row must be adjacent"
+        ld = S_local.stride(0) if nrows > 1 else max(S_local.stride(0), Ni)
+        have = S_local.untyped_storage().nbytes() // 4 - S_local.storage_offset()
+        assert ld >= Ni and (nrows - 1) * ld + Ni <= have, "S_local does not cover %d rows of %d scores %d apart" % (nrows, Ni, ld)
+    assert caption_image.is_cuda and caption_image.dtype == torch.int32 and tuple(caption_image.shape) == (Nc,) and caption_image.is_contiguous()
+    image_ptr, image_captions = _ranks_csr(caption_image, Ni)
+    rank_ir, target_key = torch.zeros(Nc, dtype=torch.int32, device=dev), torch.zeros(Nc, dtype=torch.int32, device=dev)
+    topk_ir = torch.zeros(Nc, max(K, 0), dtype=torch.int32, device=dev)
+    sh = RanksShard(S_local, ld, row0, nrows, Nc, Ni, K, rank_ir, topk_ir, target_key, image_ptr, image_captions)
+    a = sh.args(caption_image=ptr(caption_image), rank_ir=ptr(rank_ir), topk_ir=ptr(topk_ir) if K > 0 else None, target_key=ptr(target_key))
+    check(L.lib.vk_retrieval_ranks_shard_rows(C.byref(a), stream_ptr()))
+    return sh
+
+
+def retrieval_ranks_shard_counts(shard, target_key_all, out=None):
+    """vk_retrieval_ranks_shard_cols: the shard's part of the column counts.  target_key_all int32 [Nc]: the sum of every shard's
+    `target_key` -> count int32 [Nc] (one word per CSR entry); the sum of all shards' counts is the unsharded count array.  `out`: a count
+    array to ADD to instead of a fresh one (VK_RANKS_ACCUMULATE: several local blocks on one device).  One memset (without `out`) and one
+    launch (none for an empty shard), no host synchronisation."""
+    sh = shard
+    assert isinstance(sh, RanksShard), "shard: what retrieval_ranks_shard returned"
+    for t, what in ((target_key_all, "target_key_all"), (out, "out")):
+        assert t is None or (t.is_cuda and t.dtype == torch.int32 and tuple(t.shape) == (sh.Nc,) and t.is_contiguous() and t.device == sh.S.device), \
+            "%s: a contiguous int32 [%d] tensor on the shard's device" % (what, sh.Nc)
+    assert target_key_all is not None, "target_key_all: a contiguous int32 [%d] tensor on the shard's device" % sh.Nc
+    count = out if out is not None else torch.empty(sh.Nc, dtype=torch.int32, device=sh.S.device)
+    a = sh.args(target_key=ptr(target_key_all), count=ptr(count), flags=L.RANKS_ACCUMULATE if out is not None else 0)
+    check(L.lib.vk_retrieval_ranks_shard_cols(C.byref(a), stream_ptr()))
+    return count
+
+
+def retrieval_ranks_finish(count_sum, image_ptr, Ni):
+    """vk_retrieval_ranks_finish: count_sum int32 [Nc] = the sum of all shards' counts, image_ptr int32 [Ni + 1] -> rank_tr int32 [Ni], per
+    image the minimum over its CSR entries, -1 without one.  One launch, no host synchronisation."""
+    Ni = int(Ni)
+    assert count_sum.is_cuda and count_sum.dtype == torch.int32 and count_sum.dim() == 1 and count_sum.numel() > 0 and count_sum.is_contiguous(), "count_sum: a contiguous int32 [Nc] cuda tensor"
+    assert image_ptr.dtype == torch.int32 and tuple(image_ptr.shape) == (Ni + 1,) and image_ptr.is_contiguous() and image_ptr.device == count_sum.device, "image_ptr: int32 [Ni + 1] beside count_sum"
+    rank_tr = torch.empty(Ni, dtype=torch.int32, device=count_sum.device)
+    a = L.RetrievalRanksShardArgs(image_ptr=ptr(image_ptr), count=ptr(count_sum), rank_tr=ptr(rank_tr), Nc=count_sum.numel(), Ni=Ni)
+    check(L.lib.vk_retrieval_ranks_finish(C.byref(a), stream_ptr()))
+    return rank_tr
 
 
 def image_means(feat, n):

@@ -20,7 +20,9 @@ refreshes them).  Handles hold prefix outputs computed with the weights of the t
 
 `evaluate_retrieval(model, dset_val, task_id)` is the whole of eval_retrieval.py:161-263 on top of it: the device arrays of a
 `volta_amd.datasets.RetrievalDatasetVal`, the score matrix, `ops.retrieval_ranks` (csrc/ranks.hip: ranks and top-k by counting keys, no sort)
-and one transfer of the integer ranks; the recall / rank numbers are the driver's own float64 arithmetic on that copy.
+and one transfer of the integer ranks; the recall / rank numbers are the driver's own float64 arithmetic on that copy.  With `group=` the
+captions are sharded over the ranks of a process group and the ranks' parts are merged exactly (`ops.retrieval_ranks_shard` and its two
+companions, four integer all_reduce calls).
 """
 import ctypes as C
 
@@ -276,14 +278,66 @@ def rank_metrics(ranks):
 
 class RetrievalResult:
     """image_retrieval / text_retrieval: dicts of r1, r5, r10, medr, meanr; results: per caption the top-k image indices (what the driver
-    dumps into *_result.json); rank_ir [Nc], rank_tr [Ni] int32 and score_matrix [Nc, Ni] fp32 stay on the device."""
+    dumps into *_result.json); rank_ir [Nc], rank_tr [Ni] int32 and score_matrix fp32 stay on the device.  score_matrix holds the rows
+    caption_range = (first caption, one past the last) of the [Nc, Ni] matrix: all of them, (0, Nc), unless the evaluation was sharded."""
 
-    def __init__(self, image_retrieval, text_retrieval, results, rank_ir, rank_tr, score_matrix):
+    def __init__(self, image_retrieval, text_retrieval, results, rank_ir, rank_tr, score_matrix, caption_range=None):
         self.image_retrieval, self.text_retrieval, self.results = image_retrieval, text_retrieval, results
         self.rank_ir, self.rank_tr, self.score_matrix = rank_ir, rank_tr, score_matrix
+        self.caption_range = (0, int(rank_ir.numel())) if caption_range is None else caption_range
 
 
-def evaluate_retrieval(model, dset_val, task_id=None, pair_chunk=1000, topk=20):
+def _process_group(group):
+    """(torch.distributed, the group or None for the default one) of evaluate_retrieval's `group` argument"""
+    import torch.distributed as dist
+    if not (dist.is_available() and dist.is_initialized()):
+        raise ValueError("evaluate_retrieval: group=%r was given, but torch.distributed is not initialised (init_process_group first)" % (group,))
+    if group is True:
+        return dist, None
+    if group is False or not isinstance(group, dist.ProcessGroup):
+        raise ValueError("evaluate_retrieval: group must be None, True (the default process group) or a torch.distributed group, not %r" % (group,))
+    return dist, group
+
+
+def _all_reduce_sum(dist, pg, t):
+    """in-place integer sum of `t` over the group; staged through the host when the backend does not reduce device tensors"""
+    if t.numel() == 0:                               # the same on every rank: nobody enters the collective
+        return t
+    if "nccl" in str(dist.get_backend(pg)):
+        dist.all_reduce(t, op=dist.ReduceOp.SUM, group=pg)
+    else:
+        h = t.cpu()
+        dist.all_reduce(h, op=dist.ReduceOp.SUM, group=pg)
+        t.copy_(h)
+    return t
+
+
+def _ranks_sharded(scorer, arr, K, dist, pg, phase_hook):
+    """The score block of this rank's captions and the exact merge of all ranks' parts ("Sharded over ranks"):
+    -> rank_ir, topk_ir, rank_tr (the same on every rank), S_local, (row0, row1)"""
+    from . import ops
+    mark = phase_hook if phase_hook is not None else (lambda name: None)
+    rank, W = dist.get_rank(pg), dist.get_world_size(pg)
+    Nc = int(arr["input_ids"].shape[0])
+    row0, row1 = rank * Nc // W, (rank + 1) * Nc // W
+    caps = scorer.encode_captions(arr["input_ids"][row0:row1], arr["segment_ids"][row0:row1], arr["input_mask"][row0:row1]) if row1 > row0 else None
+    imgs = scorer.encode_images(arr["features"], arr["spatials"], arr["image_mask"])
+    mark("encode")
+    if caps is not None:
+        S = scorer.score_matrix(caps, imgs)
+    else:                                            # more ranks than captions: this one scores nothing and still takes part in the sums
+        S = torch.empty(0, imgs.n, dtype=torch.float32, device=scorer.device)
+    mark("score")
+    sh = ops.retrieval_ranks_shard(S, row0, Nc, arr["caption_image"], K)
+    target_key = _all_reduce_sum(dist, pg, sh.target_key)
+    count = _all_reduce_sum(dist, pg, ops.retrieval_ranks_shard_counts(sh, target_key))
+    rank_tr = ops.retrieval_ranks_finish(count, sh.image_ptr, imgs.n)
+    rank_ir, topk_ir = _all_reduce_sum(dist, pg, sh.rank_ir), _all_reduce_sum(dist, pg, sh.topk_ir)
+    mark("ranks")
+    return rank_ir, topk_ir, rank_tr, S, (row0, row1)
+
+
+def evaluate_retrieval(model, dset_val, task_id=None, pair_chunk=1000, topk=20, group=None, phase_hook=None):
     """eval_retrieval.py:161-263 for a `RetrievalDatasetVal`: image retrieval (per caption, the rank of its image) and text retrieval (per
     image, the best rank of one of its captions) as recall@1/5/10, median and mean rank, plus the top-`topk` images per caption.
 
@@ -291,26 +345,39 @@ def evaluate_retrieval(model, dset_val, task_id=None, pair_chunk=1000, topk=20):
     volta_amd.parallel.DistributedDataParallel; what RetrievalScorer refuses is refused here with its messages, and the model's state is
     left alone as the scorer leaves it.  Any number of captions and images (COCO's 5k test set is the same call).
 
+    `group`: None scores everything on this device, also inside an initialised process group.  True (the default process group) or a
+    torch.distributed group shards the captions: every rank of the group must make the same call; rank r of W encodes all images and the
+    captions [r * Nc // W, (r + 1) * Nc // W) (none when W > Nc), fills that block of the matrix, and four all_reduce(SUM) calls over small
+    integer arrays merge the ranks' parts exactly (csrc/ranks.hip, the shard calls).  Every rank returns the same metrics, `results`,
+    `rank_ir` and `rank_tr` -- the bits of the unsharded call on the same scores; `score_matrix` is the rank's own block, the rows
+    `caption_range`.  A group of one rank takes this path too.  `phase_hook(name)`, sharded path only, is called when "encode", "score" and
+    "ranks" (kernels and exchange) have been issued: a timer's hook synchronises the device itself (tools/eval_retrieval_sharded.py).
+
     Ties: ranks follow np.argsort(-s, kind="stable") with NaN last (ops.retrieval_ranks).  The driver's np.argsort(-s) is not stable, so
     its rank is only defined where the target's score is untied; there the two agree.  Images without a caption are left out of the
     text-retrieval statistics (the driver's `min(ranks)` fails on them)."""
     from . import ops
     from .parallel import DistributedDataParallel
+    dist, pg = _process_group(group) if group is not None else (None, None)
     if isinstance(model, DistributedDataParallel):
         model = model.module
     scorer = RetrievalScorer(model, task_id, pair_chunk=pair_chunk)
     if not 0 <= int(topk) <= 64:
         raise ValueError("topk must be in 0..64, got %r" % (topk,))
     arr = dset_val.device_arrays(scorer.device)
-    caps = scorer.encode_captions(arr["input_ids"], arr["segment_ids"], arr["input_mask"])
-    imgs = scorer.encode_images(arr["features"], arr["spatials"], arr["image_mask"])
-    S = scorer.score_matrix(caps, imgs)
-    rank_ir, topk_ir, rank_tr = ops.retrieval_ranks(S, arr["caption_image"], int(topk))
+    if dist is None:
+        caps = scorer.encode_captions(arr["input_ids"], arr["segment_ids"], arr["input_mask"])
+        imgs = scorer.encode_images(arr["features"], arr["spatials"], arr["image_mask"])
+        S = scorer.score_matrix(caps, imgs)
+        rank_ir, topk_ir, rank_tr = ops.retrieval_ranks(S, arr["caption_image"], int(topk))
+        caption_range = None
+    else:
+        rank_ir, topk_ir, rank_tr, S, caption_range = _ranks_sharded(scorer, arr, int(topk), dist, pg, phase_hook)
     Nc, Ni, K = rank_ir.numel(), rank_tr.numel(), int(topk)
     host = torch.cat([rank_ir, rank_tr, topk_ir.reshape(-1)]).cpu().numpy()          # the one transfer
     ir, tr, top = host[:Nc], host[Nc:Nc + Ni], host[Nc + Ni:].reshape(Nc, K)
     results = [[int(v) for v in row if v >= 0] for row in top]
-    return RetrievalResult(rank_metrics(ir), rank_metrics(tr[tr >= 0]), results, rank_ir, rank_tr, S)
+    return RetrievalResult(rank_metrics(ir), rank_metrics(tr[tr >= 0]), results, rank_ir, rank_tr, S, caption_range)
 
 
 # ------------------------------------------------------------------------------------------------ the hard-negative pool of the training set
