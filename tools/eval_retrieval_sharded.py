@@ -1,6 +1,6 @@
 """Runs and times the retrieval evaluation with the captions sharded over W ranks (`evaluate_retrieval(..., group=True)`):
 
-  python tools/eval_retrieval_sharded.py [--world W] [--images 1000] [--config ctrl_vilbert_base] [--reps 2] [--timeout 900] [--out FILE.json]
+  python tools/eval_retrieval_sharded.py [--world W] [--images 1000] [--config ctrl_vilbert_base] [--dtype bf16|fp8] [--reps 2] [--timeout 900] [--out FILE.json]
   python tools/eval_retrieval_sharded.py --kernels [--reps 20] [--out FILE.json]
 
 Default mode.  Writes the synthetic store of tools/bench_retrieval_eval.py (`--images` images of 36 regions x 2048 features, five 12-word
@@ -11,7 +11,8 @@ speed-up).  Every rank builds the same randomly initialised task model (one seed
 times; the first call builds the scorer's plans and is reported apart.  Per rank and call it prints the seconds of three phases, taken by a
 `phase_hook` that synchronises the device: encode (all images and the rank's captions), score (the rank's block of the matrix), ranks +
 exchange (three launches and four all_reduce calls), and inside the last the seconds spent in `all_reduce` itself.  The parent checks
-that every rank reports the same metrics and prints one JSON line.
+that every rank reports the same metrics and prints one JSON line.  `--dtype fp8` scores on the e4m3 projection path
+(`evaluate_retrieval(..., projection_dtype="fp8")`): the metrics are then the fp8 model's.
 
 --kernels.  One process, one GPU, no model: `ops.retrieval_ranks` against the W = 1 sharded sequence (`retrieval_ranks_shard`,
 `retrieval_ranks_shard_counts`, `retrieval_ranks_finish`) on the matrices of tools/bench_retrieval_eval.py, 5000 x 1000 and 25000 x 5000,
@@ -106,7 +107,7 @@ def child(args):
             dist.barrier()
             torch.cuda.synchronize()
             reduce_s[0], spent["_t"] = 0.0, time.perf_counter()
-            res = evaluate_retrieval(model, ds, task_id="TASK8", pair_chunk=args.pair_chunk, topk=20, group=True, phase_hook=hook)
+            res = evaluate_retrieval(model, ds, task_id="TASK8", pair_chunk=args.pair_chunk, topk=20, group=True, phase_hook=hook, projection_dtype=args.dtype)
             calls.append(dict(encode=spent["encode"], score=spent["score"], ranks=spent["ranks"], all_reduce=reduce_s[0]))
             print("rank %d call %d: captions [%d, %d): encode %.3f s, score %.3f s, ranks + exchange %.4f s (all_reduce %.4f s)%s" % (
                 args.rank, rep, *res.caption_range, *[calls[-1][k] for k in ("encode", "score", "ranks", "all_reduce")], "  [builds the plans]" if rep == 0 else ""), flush=True)
@@ -129,7 +130,7 @@ def parent(args):
         write_store(root, args.images)
         procs = [subprocess.Popen(["timeout", "-k", "10", str(args.timeout), sys.executable, os.path.abspath(__file__), "--child", "--rank", str(r), "--world", str(W),
                                    "--root", root, "--backend", backend, "--config", args.config, "--reps", str(args.reps), "--timeout", str(args.timeout),
-                                   "--pair-chunk", str(args.pair_chunk)]) for r in range(W)]
+                                   "--pair-chunk", str(args.pair_chunk), "--dtype", args.dtype]) for r in range(W)]
         pending, failed = set(range(W)), None
         while pending and failed is None:
             for r in sorted(pending):
@@ -149,7 +150,7 @@ def parent(args):
         ranks = [json.load(open(os.path.join(root, "rank%d.json" % r))) for r in range(W)]
     for r in ranks[1:]:
         assert r["image_retrieval"] == ranks[0]["image_retrieval"] and r["text_retrieval"] == ranks[0]["text_retrieval"], "the ranks disagree"
-    res = dict(world=W, gpus=ngpu, backend=backend, images=args.images, captions=args.images * SENTENCES, config=args.config, ranks=ranks)
+    res = dict(world=W, gpus=ngpu, backend=backend, images=args.images, captions=args.images * SENTENCES, config=args.config, dtype=args.dtype, ranks=ranks)
     print(json.dumps(res))
     return res
 
@@ -197,6 +198,7 @@ def main():
     ap.add_argument("--world", type=int, default=0)
     ap.add_argument("--images", type=int, default=1000)
     ap.add_argument("--config", default="ctrl_vilbert_base")
+    ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp8"], help="projection precision of the scorer")
     ap.add_argument("--reps", type=int, default=0)
     ap.add_argument("--timeout", type=int, default=900)
     ap.add_argument("--pair-chunk", type=int, default=1000)

@@ -232,12 +232,51 @@ class Stream:
         self.L, self.M, self.H = L_, B * L_, H
 
 
+def wide_geometry(cfg):
+    """None for the single-width geometry of the ctrl_* configs (both streams one hidden size, 64-wide heads, no per-sub-layer widths), else
+    a description of what differs (config/vilbert_base.json: 768 text, 1024 vision, sub-layer widths of their own).  The e4m3 projection
+    path covers the single-width geometry only."""
+    H, Hv = cfg.hidden_size, cfg.v_hidden_size
+    what = []
+    if H != Hv:
+        what.append("stream widths %d text / %d vision" % (H, Hv))
+    per = [k for k in ("sublayer2attn_hidden_size", "sublayer2num_attention_heads", "sublayer2intermediate_size", "sublayer2v_attn_hidden_size",
+                       "sublayer2v_num_attention_heads", "sublayer2v_intermediate_size") if getattr(cfg, k)]
+    if per:
+        what.append("per-sub-layer widths (%s)" % ", ".join(per))
+    if H // cfg.num_attention_heads != 64 or Hv // cfg.v_num_attention_heads != 64:
+        what.append("head sizes %d text / %d vision, not 64" % (H // cfg.num_attention_heads, Hv // cfg.v_num_attention_heads))
+    return "; ".join(what) if what else None
+
+
+def pair_segments(split, fp8=False):
+    """[(name, side 0 caption | 1 image)]: the gather segments of a score pair plan, in the order of its `pair_inputs` -- what one
+    vk_pair_gather launch copies per pair out of the encoded handles.  split = retrieval.split_plan(cfg).  On the e4m3 path a modality whose
+    prefix ends in a sub-layer also hands over the e4m3 copy its last LayerNorm wrote and that copy's row scales (x8_*, xs_*): the pair plan's
+    first projection must read those bits, as the whole-model plan does, not a re-quantisation of the bf16 rows.  A modality whose prefix
+    is its embedding alone hands over nothing more; the pair plan quantises its gathered bf16 rows itself.  At most VK_PAIR_MAX_SEGS."""
+    text_subs, vision_subs, per_modality = split
+    if per_modality:
+        segs = [("x_t", 0), ("x_v", 1)]
+    else:
+        segs = [("input_ids", 0), ("token_type_ids", 0), ("image_feat", 1), ("image_loc", 1)]
+    segs += [("attention_mask", 0), ("image_attention_mask", 1)]
+    if fp8 and per_modality:
+        if text_subs:
+            segs += [("x8_t", 0), ("xs_t", 0)]
+        if vision_subs:
+            segs += [("x8_v", 1), ("xs_v", 1)]
+    assert len(segs) <= L.PAIR_MAX_SEGS
+    return segs
+
+
 class StepEngine:
     """Buffers + forward / backward command lists of one (B, T, Rv, train) shape."""
 
     H8_MUL = 8.0           # static scale of the fp8 copy of the GELU output: |h| <= 56 representable, 2^-9 absolute resolution near 0
 
-    def __init__(self, cfg, arena, B, T, Rv, train, heads="pretrain", fp8=False, task=None, task_dropout=0.1, attn_maps=False, part=None, split=None):
+    def __init__(self, cfg, arena, B, T, Rv, train, heads="pretrain", fp8=False, task=None, task_dropout=0.1, attn_maps=False, part=None, split=None,
+                 projection_dtype=None):
         """fp8: the forward Q|K|V, FFN-up and FFN-down projections of every sub-layer run on the e4m3 MFMA path (csrc/fp8.hip); inputs are
         quantised per row right before the GEMM, weights per output channel whenever they change; the backward stays bf16.
         heads: "pretrain" = the three pre-training heads and losses (BertForVLPreTraining); "tasks" = poolers only, the
@@ -246,19 +285,24 @@ class StepEngine:
         "score" = one forward-only list of the retrieval scorer (volta_amd/retrieval.py), eval semantics, no backward: `part` "text" (text
         embedding + the text-only sub-layers, B captions), "image" (image embedding + the vision-only sub-layers, B images) or "pair" (the
         mixing suffix on B pairs whose inputs vk_pair_gather wrote into `pair_inputs`, poolers, fusion and the scoring head: `task`'s
-        VL-logit classifier, or cls.bi_seq_relationship when task is None); `split` = retrieval.split_plan(cfg)."""
+        VL-logit classifier, or cls.bi_seq_relationship when task is None); `split` = retrieval.split_plan(cfg).
+        projection_dtype: score plans only, None | "bf16" | "fp8" -- the scorer's own precision switch (the `fp8` argument belongs to the
+        training plans and stays refused here).  "fp8" builds the same e4m3 launches as `fp8` does for a whole-model plan; a prefix plan then
+        exposes the e4m3 copy its last LayerNorm wrote as `score_x8`, and the pair plan starts from gathered copies (`pair_segments`)."""
         self.cfg, self.arena, self.B, self.T, self.Rv, self.train = cfg, arena, B, T, Rv, train
         self.heads = heads
         self.part, self.split = part, split
         self.fwd_only = heads == "score"   # the builders return before their backward part
         self.only = None                   # score prefixes: the one stream (0 text, 1 vision) whose problems a sub-layer emits
         if self.fwd_only and (train or fp8 or attn_maps or part not in ("text", "image", "pair") or split is None):
-            raise ValueError("a score plan is an eval-mode bf16 forward of part text | image | pair with a split plan")
+            raise ValueError("a score plan is an eval-mode forward of part text | image | pair with a split plan; its precision is projection_dtype, not fp8")
+        if projection_dtype not in (None, "bf16", "fp8") or (projection_dtype is not None and not self.fwd_only):
+            raise ValueError("projection_dtype %r: None | 'bf16' | 'fp8', for heads='score' plans only" % (projection_dtype,))
         self.task = task              # heads == "tasks": (task id, its task_cfg entry) -- the classifier built behind the poolers
         self.attn_maps = bool(attn_maps)      # keep every attention sub-layer's probabilities (config.visualization, encoders.py:342-358): generic attention kernels
         self.attn_map_info = []
         self.task_dropout = float(task_dropout)      # BertForVLTasks(dropout_prob=...): nn.Dropout on the fused pooled vector / region states (encoders.py:1118-1122)
-        self.fp8 = bool(fp8)
+        self.fp8 = bool(fp8) or projection_dtype == "fp8"
         # soft boundaries between dependent GEMMs (VK_GEMM_SOFT_START + row-block counters).  OFF by default: measured neutral in the step
         # (profiles/r04_experiments.md: on gfx950 a barrier-less dispatch starts on an XCD only when that XCD's workgroups of the launch in
         # front are done, so there is no tail overlap to win, and the write-through hand-off costs what the shorter boundary saves)
@@ -294,10 +338,8 @@ class StepEngine:
         # the MFMA attention kernels, 32 / 96 / 128 on the generic ones.
         if H % 64 or Hv % 64 or H > 1024 or Hv > 1024:
             raise NotImplementedError("hidden sizes must be multiples of 64, at most 1024 (got %d / %d)" % (H, Hv))
-        self.wide = H != Hv or bool(cfg.sublayer2attn_hidden_size or cfg.sublayer2num_attention_heads or cfg.sublayer2intermediate_size or
-                                    cfg.sublayer2v_attn_hidden_size or cfg.sublayer2v_num_attention_heads or cfg.sublayer2v_intermediate_size) or \
-            H // cfg.num_attention_heads != 64 or Hv // cfg.v_num_attention_heads != 64
-        if self.wide and fp8:
+        self.wide = wide_geometry(cfg) is not None
+        if self.wide and self.fp8:
             raise NotImplementedError("the fp8 projection path covers the single-width (ctrl_*) geometry")
         if self.wide and cfg.image_embeddings != "vilbert":
             raise NotImplementedError("different stream widths are built for the ViLBERT embeddings (config/vilbert_base.json)")
@@ -703,16 +745,20 @@ class StepEngine:
             sublayers(subs)
             self.only = None
             self.score_out = self.x[m]
+            self.score_x8 = self.x8[m]     # e4m3 path, prefix ending in a sub-layer: (copy, row scales) its LayerNorm wrote; else None
         else:
             i64, f32 = torch.int64, torch.float32
             raw = [self.buf("pair_mask_t", (B, T), i64), self.buf("pair_mask_v", (B, Rv), i64)]
-            if per_modality:
-                ins = [("x_t", self.buf("pair_x_t", (B * T, self.st[0].H)), 0), ("x_v", self.buf("pair_x_v", (B * Rv, self.st[1].H)), 1)]
-            else:
-                ins = [("input_ids", self.buf("pair_ids", (B, T), i64), 0), ("token_type_ids", self.buf("pair_type_ids", (B, T), i64), 0),
-                       ("image_feat", self.buf("pair_feat", (B, Rv, cfg.v_feature_size), f32), 1),
-                       ("image_loc", self.buf("pair_loc", (B, Rv, cfg.num_locs), f32), 1)]
-            self.pair_inputs = ins + [("attention_mask", raw[0], 0), ("image_attention_mask", raw[1], 1)]
+            u8, Hp = torch.uint8, _round_up(self.H, 128)
+            make = {"x_t": lambda: self.buf("pair_x_t", (B * T, self.st[0].H)), "x_v": lambda: self.buf("pair_x_v", (B * Rv, self.st[1].H)),
+                    "input_ids": lambda: self.buf("pair_ids", (B, T), i64), "token_type_ids": lambda: self.buf("pair_type_ids", (B, T), i64),
+                    "image_feat": lambda: self.buf("pair_feat", (B, Rv, cfg.v_feature_size), f32),
+                    "image_loc": lambda: self.buf("pair_loc", (B, Rv, cfg.num_locs), f32),
+                    "attention_mask": lambda: raw[0], "image_attention_mask": lambda: raw[1],
+                    "x8_t": lambda: self.buf("pair_x8_t", (B * T, Hp), u8), "xs_t": lambda: self.buf("pair_xs_t", (B * T,), f32),
+                    "x8_v": lambda: self.buf("pair_x8_v", (B * Rv, Hp), u8), "xs_v": lambda: self.buf("pair_xs_v", (B * Rv,), f32)}
+            self.pair_inputs = [(name, make[name](), side) for name, side in pair_segments(self.split, self.fp8)]
+            ins = {name: t for name, t, _ in self.pair_inputs}
             a = self.pair_args = self.k(L.PairGatherArgs())
             for k, (_, t, side) in enumerate(self.pair_inputs):
                 a.dst[k], a.bytes[k], a.side[k] = t.data_ptr(), t.numel() * t.element_size() // B, side
@@ -720,7 +766,9 @@ class StepEngine:
             mask_prep(0, raw[0])
             mask_prep(1, raw[1])
             if per_modality:
-                self.x = [ins[0][1], ins[1][1]]
+                self.x = [ins["x_t"], ins["x_v"]]
+                # the hand-over: the gathered copy of the prefix LayerNorm's e4m3 output, or None (the first projection quantises x itself)
+                self.x8 = [(ins["x8_" + c], ins["xs_" + c]) if "x8_" + c in ins else None for c in "tv"]
             elif kind == "visualbert":
                 self._emb_visualbert("bert.embeddings.")
             else:

@@ -7,6 +7,13 @@ two-stream model the sub-layers in front of the first cross-attention depend on 
 (csrc/pairs.hip).  Every launch of these plans is a launch of the model's own forward at another batch size: eval semantics, bf16
 activations, no dropout, no backward.
 
+Precision: `projection_dtype="fp8"` runs the Q|K|V and feed-forward projections of every scored sub-layer on the e4m3 MFMA path
+(csrc/fp8.hip), whatever the model's own `set_projection_dtype` switch says; a pair's logit is then bit for bit what the driver's loop gets
+from the model after `set_projection_dtype("fp8")` -- the fp8 model's scores and ranks, not the bf16 model's.  "bf16" asks for the bf16
+projections explicitly; None is bf16 too, but refuses a model whose own switch was left on fp8.  Where a prefix ends in a sub-layer, the
+e4m3 copy its last LayerNorm wrote (and the copy's row scales) is kept in the handle and gathered per pair, so that the suffix's first
+projection reads the bits the whole model reads there (`engine.pair_segments`).
+
     scorer = RetrievalScorer(model, task_id="TASK8", pair_chunk=1000)
     caps = scorer.encode_captions(input_ids, segment_ids, input_mask)      # [Nc, T] each, on the GPU
     imgs = scorer.encode_images(features, spatials, image_mask)            # [Ni, R, 2048], [Ni, R, num_locs], [Ni, R]
@@ -70,8 +77,16 @@ class Items:
         return self.n
 
 
+def pair_gather_segments(config, projection_dtype=None):
+    """[(name, side 0 caption | 1 image)]: what one vk_pair_gather launch copies per pair for this config and precision (host only)."""
+    from .engine import pair_segments
+    if projection_dtype not in (None, "bf16", "fp8"):
+        raise ValueError("projection_dtype %r: None | 'bf16' | 'fp8'" % (projection_dtype,))
+    return pair_segments(split_plan(config), projection_dtype == "fp8")
+
+
 class RetrievalScorer:
-    def __init__(self, model, task_id=None, pair_chunk=1000):
+    def __init__(self, model, task_id=None, pair_chunk=1000, projection_dtype=None):
         from .modeling import BertForVLPreTraining, BertForVLTasks
         if isinstance(model, BertForVLTasks):
             if task_id not in model.task_cfg or task_id not in model.clfs_dict:
@@ -88,8 +103,16 @@ class RetrievalScorer:
         cfg = model.config
         if cfg.fusion_method not in ("mul", "sum", "text"):
             raise ValueError("fusion method %r has no ITM head (encoders.py:744-747, 1192-1193)" % cfg.fusion_method)
-        if model.__dict__.get("_fp8", False):
-            raise NotImplementedError("the retrieval scorer runs the bf16 projections; set_projection_dtype('bf16') first")
+        if projection_dtype not in (None, "bf16", "fp8"):
+            raise ValueError("projection_dtype %r: None | 'bf16' | 'fp8'" % (projection_dtype,))
+        self.projection_dtype = projection_dtype
+        self._refuse_model_switch(model)
+        self.fp8 = projection_dtype == "fp8"
+        if self.fp8:
+            from .engine import wide_geometry
+            wide = wide_geometry(cfg)
+            if wide is not None:
+                raise NotImplementedError("projection_dtype='fp8': the e4m3 projection path covers the single-width (ctrl_*) geometry, not %s" % wide)
         if int(pair_chunk) < 1:
             raise ValueError("pair_chunk must be positive, got %r" % (pair_chunk,))
         self.device = next(model.parameters()).device
@@ -104,15 +127,22 @@ class RetrievalScorer:
         self._arena, self._engines = None, {}
 
     # ------------------------------------------------------------------ plumbing
+    def _refuse_model_switch(self, model):
+        """Without an explicit projection_dtype the scorer is bf16 and will not guess for a model whose own switch says fp8."""
+        if self.projection_dtype is None and model.__dict__.get("_fp8", False):
+            raise NotImplementedError("the retrieval scorer runs the bf16 projections unless told otherwise and the model's switch is on fp8: "
+                                      "pass projection_dtype='fp8' or 'bf16', or set_projection_dtype('bf16') first")
+
     def _prepare(self):
-        """The model's arena with current bf16 weights; the scorer's plans are rebuilt when the arena was."""
-        if self.model.__dict__.get("_fp8", False):
-            raise NotImplementedError("the retrieval scorer runs the bf16 projections; set_projection_dtype('bf16') first")
+        """The model's arena with current bf16 (and, for an fp8 scorer, e4m3) weights; the scorer's plans are rebuilt when the arena was."""
+        self._refuse_model_switch(self.model)
         arena = self.model.materialize()
         if arena is not self._arena:
             self._arena, self._engines = arena, {}
         arena.sync_optimizer()           # a pipelined optimizer step still in flight: every plan here reads all of the weights
         arena.refresh_shadow()
+        if self.fp8:
+            arena.refresh_fp8()          # no launch unless the weights changed (weights_epoch) or a plan registered new sites
         return arena
 
     def _engine(self, part, B, T, Rv):
@@ -120,9 +150,37 @@ class RetrievalScorer:
         key = (part, B, T, Rv)
         eng = self._engines.get(key)
         if eng is None:
-            eng = StepEngine(self.cfg, self._arena, B, T, Rv, False, heads="score", task=self.task if part == "pair" else None, part=part, split=self.split)
+            eng = StepEngine(self.cfg, self._arena, B, T, Rv, False, heads="score", task=self.task if part == "pair" else None, part=part, split=self.split,
+                             projection_dtype="fp8" if self.fp8 else "bf16")
             self._engines[key] = eng
+            if self.fp8:
+                self._arena.refresh_fp8()        # building the plan registered its weights' e4m3 sites: quantise them before its first run
         return eng
+
+    def _run_prefix(self, part, tensors, n, length, H, tag):
+        """The prefix plan of `part` over n items in chunks: x_<tag> bf16 [n * length, H] and, where the plan's last LayerNorm wrote an e4m3
+        copy (fp8 scorer, prefix ending in a sub-layer), x8_<tag> uint8 [n * length, round_up(H, 128)] and its row scales xs_<tag> fp32."""
+        self._prepare()
+        x = torch.empty(n * length, H, dtype=torch.bfloat16, device=self.device)
+        x8 = xs = None
+        for i0 in range(0, n, self.pair_chunk):
+            nb = min(self.pair_chunk, n - i0)
+            eng = self._engine(part, nb, length, 1) if part == "text" else self._engine(part, nb, 1, length)
+            eng.bind_inputs({k: v[i0:i0 + nb] for k, v in tensors.items()})
+            eng.fwd.run()
+            r0, r1 = i0 * length, (i0 + nb) * length
+            x[r0:r1].copy_(eng.score_out)
+            if eng.score_x8 is not None:
+                q, sc = eng.score_x8
+                if x8 is None:
+                    x8 = torch.empty(n * length, q.shape[1], dtype=torch.uint8, device=self.device)
+                    xs = torch.empty(n * length, dtype=torch.float32, device=self.device)
+                x8[r0:r1].copy_(q)
+                xs[r0:r1].copy_(sc)
+        out = {"x_" + tag: x}
+        if x8 is not None:
+            out["x8_" + tag], out["xs_" + tag] = x8, xs
+        return out
 
     def _tensor(self, x, dtype, shape, what):
         if not isinstance(x, torch.Tensor):
@@ -143,16 +201,7 @@ class RetrievalScorer:
         mask = self._tensor(input_mask, torch.int64, (Nc, T), "input_mask") if input_mask is not None else torch.ones_like(ids)
         tensors = dict(input_ids=ids, token_type_ids=tt, attention_mask=mask)
         if self.split[2]:
-            self._prepare()
-            H = self.cfg.hidden_size
-            x = torch.empty(Nc * T, H, dtype=torch.bfloat16, device=self.device)
-            for c0 in range(0, Nc, self.pair_chunk):
-                nb = min(self.pair_chunk, Nc - c0)
-                eng = self._engine("text", nb, T, 1)
-                eng.bind_inputs({k: v[c0:c0 + nb] for k, v in tensors.items()})
-                eng.fwd.run()
-                x[c0 * T:(c0 + nb) * T].copy_(eng.score_out)
-            tensors["x_t"] = x
+            tensors.update(self._run_prefix("text", dict(tensors), Nc, T, self.cfg.hidden_size, "t"))
         return Items(self, 0, Nc, T, tensors)
 
     def encode_images(self, features, spatials, image_mask=None):
@@ -164,16 +213,7 @@ class RetrievalScorer:
         mask = self._tensor(image_mask, torch.int64, (Ni, Rv), "image_mask") if image_mask is not None else torch.ones(Ni, Rv, dtype=torch.int64, device=self.device)
         tensors = dict(image_feat=feat, image_loc=loc, image_attention_mask=mask)
         if self.split[2]:
-            self._prepare()
-            Hv = self.cfg.v_hidden_size
-            x = torch.empty(Ni * Rv, Hv, dtype=torch.bfloat16, device=self.device)
-            for i0 in range(0, Ni, self.pair_chunk):
-                nb = min(self.pair_chunk, Ni - i0)
-                eng = self._engine("image", nb, 1, Rv)
-                eng.bind_inputs({k: v[i0:i0 + nb] for k, v in tensors.items()})
-                eng.fwd.run()
-                x[i0 * Rv:(i0 + nb) * Rv].copy_(eng.score_out)
-            tensors["x_v"] = x
+            tensors.update(self._run_prefix("image", dict(tensors), Ni, Rv, self.cfg.v_hidden_size, "v"))
         return Items(self, 1, Ni, Rv, tensors)
 
     # ------------------------------------------------------------------ pairs
@@ -185,8 +225,8 @@ class RetrievalScorer:
         if caps.length + imgs.length > 512:
             raise ValueError("%d text + %d region rows: more than 512 keys per query row" % (caps.length, imgs.length))
 
-    def _run_pairs(self, caps, imgs, npairs, cross=None, idx=None):
-        """One pair chunk: gather, then the suffix list.  -> fp32 logits [npairs, classes] (a view of the plan's output buffer)."""
+    def _gather_pairs(self, caps, imgs, npairs, cross=None, idx=None):
+        """The vk_pair_gather launch of one pair chunk into the inputs of its plan, which is returned."""
         eng = self._engine("pair", npairs, caps.length, imgs.length)
         a = eng.pair_args
         for k, (name, _, side) in enumerate(eng.pair_inputs):
@@ -200,8 +240,21 @@ class RetrievalScorer:
             a.c0 = a.nc = a.i0 = a.ni = 0
         from . import _lib as L
         L.check(L.lib.vk_pair_gather(C.byref(a), L.stream_ptr()))
+        return eng
+
+    def _run_pairs(self, caps, imgs, npairs, cross=None, idx=None):
+        """One pair chunk: gather, then the suffix list.  -> fp32 logits [npairs, classes] (a view of the plan's output buffer)."""
+        eng = self._gather_pairs(caps, imgs, npairs, cross, idx)
         eng.fwd.run()
         return eng.score_out[:npairs, :eng.score_classes]
+
+    def _matrix_blocks(self, Nc, Ni):
+        """score_matrix's pair chunks as cross products (first caption, captions, first image, images)."""
+        P = self.pair_chunk
+        if Ni >= P or self.one_caption_per_chunk:
+            return [(c, 1, i0, min(P, Ni - i0)) for c in range(Nc) for i0 in range(0, Ni, P)]
+        per = P // Ni
+        return [(c0, min(per, Nc - c0), 0, Ni) for c0 in range(0, Nc, per)]
 
     def _scores(self, logits):
         """fp32 scores of [n, classes] logits: the VL-logit itself, or the zero-shot match probability softmax(itm)[:, 0]."""
@@ -214,17 +267,12 @@ class RetrievalScorer:
         return_logits: also the raw logits, fp32 [Nc, Ni, classes] (1 for VL-logit, the two ITM logits for zero-shot)."""
         self._check_items(caps, imgs)
         self._prepare()
-        Nc, Ni, P = caps.n, imgs.n, self.pair_chunk
+        Nc, Ni = caps.n, imgs.n
         C_ = 1 if self.task is not None else 2
         S = torch.empty(Nc, Ni, dtype=torch.float32, device=self.device)
         Lg = torch.empty(Nc, Ni, C_, dtype=torch.float32, device=self.device) if return_logits else None
-        if Ni >= P or self.one_caption_per_chunk:
-            blocks = [(c, 1, i0, min(P, Ni - i0)) for c in range(Nc) for i0 in range(0, Ni, P)]
-        else:
-            per = P // Ni
-            blocks = [(c0, min(per, Nc - c0), 0, Ni) for c0 in range(0, Nc, per)]
         with torch.no_grad():
-            for c0, nc, i0, ni in blocks:
+            for c0, nc, i0, ni in self._matrix_blocks(Nc, Ni):
                 lg = self._run_pairs(caps, imgs, nc * ni, cross=(c0, nc, i0, ni))
                 S[c0:c0 + nc, i0:i0 + ni].copy_(self._scores(lg).view(nc, ni))
                 if Lg is not None:
@@ -337,13 +385,16 @@ def _ranks_sharded(scorer, arr, K, dist, pg, phase_hook):
     return rank_ir, topk_ir, rank_tr, S, (row0, row1)
 
 
-def evaluate_retrieval(model, dset_val, task_id=None, pair_chunk=1000, topk=20, group=None, phase_hook=None):
+def evaluate_retrieval(model, dset_val, task_id=None, pair_chunk=1000, topk=20, group=None, phase_hook=None, projection_dtype=None):
     """eval_retrieval.py:161-263 for a `RetrievalDatasetVal`: image retrieval (per caption, the rank of its image) and text retrieval (per
     image, the best rank of one of its captions) as recall@1/5/10, median and mean rank, plus the top-`topk` images per caption.
 
     `model`: a BertForVLTasks with the VL-logit task `task_id`, or a BertForVLPreTraining with task_id None (zero-shot), bare or wrapped in
     volta_amd.parallel.DistributedDataParallel; what RetrievalScorer refuses is refused here with its messages, and the model's state is
     left alone as the scorer leaves it.  Any number of captions and images (COCO's 5k test set is the same call).
+
+    `projection_dtype`: None | "bf16" | "fp8", handed to the scorer.  Under "fp8" the scores, ranks and recalls are those of the model
+    with its projections on the e4m3 path (the driver's numbers after `set_projection_dtype("fp8")`), not the bf16 model's.
 
     `group`: None scores everything on this device, also inside an initialised process group.  True (the default process group) or a
     torch.distributed group shards the captions: every rank of the group must make the same call; rank r of W encodes all images and the
@@ -361,7 +412,7 @@ def evaluate_retrieval(model, dset_val, task_id=None, pair_chunk=1000, topk=20, 
     dist, pg = _process_group(group) if group is not None else (None, None)
     if isinstance(model, DistributedDataParallel):
         model = model.module
-    scorer = RetrievalScorer(model, task_id, pair_chunk=pair_chunk)
+    scorer = RetrievalScorer(model, task_id, pair_chunk=pair_chunk, projection_dtype=projection_dtype)
     if not 0 <= int(topk) <= 64:
         raise ValueError("topk must be in 0..64, got %r" % (topk,))
     arr = dset_val.device_arrays(scorer.device)
