@@ -615,7 +615,7 @@ int vk_gate_value(const uint64_t* flag, uint64_t want, int timeout_us, int32_t* 
 int vk_comm_standin(const void* src, void* dst, int64_t bytes, int nwg, int min_usec, uint64_t* stamps, vk_stream_t s);
 /* The persistent GEMM launches (one workgroup per CU, geometries 258 / 259 | VK_GEMM_PERSISTENT) leave `n` CUs (0 .. 128) unclaimed from now
  * on: room for the channel kernels of a collective that runs beside the backward pass.  The ONE piece of process-wide state in the
- * library -- a launch geometry shared by every stream, set by volta_amd.parallel.DistributedDataParallel (VK_COMM_CUS); returns the
+ * library -- a launch geometry shared by every stream.  Called by tests and tools; no product code sets it.  Returns the
  * previous value.  n < 0 only queries. */
 int vk_gemm_reserve_cus(int n);
 /* The tail of a sub-layer's weight-gradient block in ONE launch: every split-K slab sum (kind 0, as vk_sum_slabs_f32) and every

@@ -1,7 +1,6 @@
 """End-to-end parity of the HIP engine behind BertForVLPreTraining against the CPU oracle: hidden states after
 every sub-layer, the three losses and the gradient of every parameter; eval mode and training mode with the
 Philox dropout masks replayed in the oracle.  True layer widths (768 / 12 heads / 3072), reduced depth.  GPU only."""
-import numpy as np
 import pytest
 import torch
 
@@ -146,7 +145,9 @@ def _parity(name, train, B, T, Rn, batch_seed=7, max_pos=None):
 
 def test_no_labelled_rows_edge_case():
     """A batch whose pairs are all mismatched carries no MLM / region labels (train_concap.py:279-284): the reference
-    then returns NaN for the MLM mean over an empty set and 0 for the region loss; gradients stay finite here."""
+    then returns NaN for the MLM mean over an empty set and 0 for the region loss; gradients stay finite here.  Also pins two
+    properties of every plan the engine builds: no chain launch in either command list, and soft_error() (the benchmark's
+    `handoff_errors`) is 0."""
     from oracle import volta_ref as R
     model, rcfg, sd = build("vilbert")
     batch = R.synthetic_batch(rcfg, 2, 20, 36, seed=5)
@@ -159,6 +160,10 @@ def test_no_labelled_rows_edge_case():
     nsp.sum().backward()
     torch.cuda.synchronize()
     assert all(torch.isfinite(p.grad).all() for p in model.parameters())
+    from volta_amd import _lib as L
+    eng = model._last[0]
+    assert not any(op[0] == L.OP_GEMM_CHAIN for op in eng.fwd.ops + eng.bwd.ops), "the plan has no chain launch"
+    assert eng.soft_error() == 0
 
 
 def test_grad_accumulation_and_state_dict_roundtrip():
@@ -292,44 +297,3 @@ def test_attention_maps_against_oracle(name, train):
     assert out2[4] == ([None] * n_attn, [None] * n_attn)
     out3 = model2.bert(cb["input_ids"], cb["image_feat"], cb["image_loc"], cb["segment_ids"], cb["input_mask"], cb["image_mask"])
     assert out3[4] == ([], [])
-
-
-@pytest.mark.parametrize("switches", [{"VK_CHAIN": "all"}, {"VK_SOFT": "1"}])
-def test_handoff_switches_leave_the_step_unchanged(monkeypatch, switches):
-    """At the benchmark's shapes (batch 256: the only ones large enough for them) the FFN pairs as chain launches (VK_CHAIN=all: forward and
-    backward pair) or behind soft boundaries (VK_SOFT=1) give the losses and gradients of the default two fenced launches bit for bit --
-    the hand-off changes when a row block is read, never what is read -- and no waiting tile gives up."""
-    from oracle import volta_ref as R
-    from volta_amd import _lib as L
-    model, rcfg, sd = build("vilbert")
-    batch = R.synthetic_batch(rcfg, 256, 20, 36, seed=3)
-    cb = {k: v.cuda() for k, v in batch.items()}
-    args = (cb["input_ids"], cb["image_feat"], cb["image_loc"], cb["segment_ids"], cb["input_mask"], cb["image_mask"],
-            cb["lm_label_ids"], cb["image_label"], cb["image_cls"], None, None, None, None, None, cb["is_match"])
-    model.train()
-
-    def step():
-        for p in model.parameters():
-            p.grad = None
-        model.set_dropout_seed(9)
-        losses = model(*args)
-        sum(losses).sum().backward()
-        torch.cuda.synchronize()
-        return [float(l) for l in losses], {k: p.grad.clone() for k, p in model.named_parameters()}
-
-    for k in ("VK_CHAIN", "VK_SOFT"):
-        monkeypatch.delenv(k, raising=False)
-    base_losses, base = step()
-    assert not any(op[0] == L.OP_GEMM_CHAIN for op in model._last[0].fwd.ops), "the default plan has no chain launch"
-    for k, v in switches.items():
-        monkeypatch.setenv(k, v)
-    model.__dict__["_engines"] = {}                    # the plan is compiled under the switches
-    for rep in range(3):
-        losses, grads = step()
-        eng = model._last[0]
-        if "VK_CHAIN" in switches:
-            assert any(op[0] == L.OP_GEMM_CHAIN for op in eng.fwd.ops) and any(op[0] == L.OP_GEMM_CHAIN for op in eng.bwd.ops)
-        assert eng.soft_error() == 0, "a waiting tile gave up"
-        assert np.allclose(losses, base_losses, rtol=1e-5), (losses, base_losses)      # the loss sums are accumulated with atomics
-        for k, g in grads.items():
-            assert torch.equal(g, base[k]), k

@@ -303,33 +303,6 @@ class StepEngine:
         self.attn_map_info = []
         self.task_dropout = float(task_dropout)      # BertForVLTasks(dropout_prob=...): nn.Dropout on the fused pooled vector / region states (encoders.py:1118-1122)
         self.fp8 = bool(fp8) or projection_dtype == "fp8"
-        # soft boundaries between dependent GEMMs (VK_GEMM_SOFT_START + row-block counters).  OFF by default: measured neutral in the step
-        # (profiles/r04_experiments.md: on gfx950 a barrier-less dispatch starts on an XCD only when that XCD's workgroups of the launch in
-        # front are done, so there is no tail overlap to win, and the write-through hand-off costs what the shorter boundary saves)
-        self.soft = os.environ.get("VK_SOFT", "0") == "1"
-        # FFN-up -> FFN-down as ONE persistent launch with row-block hand-off (vk_gemm_chain): "0" (default) two launches; "fwd" the forward
-        # pair; "all" also the backward pair (FFN-down dgrad x gelu' -> FFN-up dgrad).  Measured (profiles/r04_experiments.md 2 and 9,
-        # r04_chain_stamps.txt): the launch boundary goes, but the workgroups with three producer tiles set the pace -- -0.08 ms per step for
-        # "fwd" while the consumer's poll was a bare counter read; with the acquire the memory model asks for behind the poll (buffer_inv:
-        # every waiting tile drops its XCD's cached operand lines) "fwd" costs +0.15 ms, "all" more.  Off: the default step has no
-        # intra-launch hand-off in it.
-        self.chain = os.environ.get("VK_CHAIN", "0")
-        self.side_delay_us = int(os.environ.get("VK_SIDE_DELAY_US", "0"))
-        if os.environ.get("VK_RESERVE_CUS"):                  # study knob: the persistent GEMM launches leave this many CUs unclaimed (process-wide)
-            L.lib.vk_gemm_reserve_cus(int(os.environ["VK_RESERVE_CUS"]))
-        # How a sub-layer's weight-gradient block (side stream) is started: "event" (default) -- the fork event of rounds 1-3; "gate" -- a
-        # one-wave gate at the head of the block that the sub-layer's last dgrad releases as its first workgroup retires, no stream event
-        # (vk_gemm_problem::retire_flag + vk_gate_wait).  Built to take the cross-queue wake-up latency out of the schedule; measured
-        # 0.1-0.2 ms per step slower than the event form and no cure for the slow steps it was built against (those came from a helper
-        # stream on the compute stream's pipe: volta_amd/streams.py, profiles/r04_experiments.md).  Kept as a switch.
-        self.side_gate = os.environ.get("VK_SIDE_START", "event") == "gate"
-        if self.side_gate:
-            # a gate on the hardware queue of the stream that releases it would wait for its own releaser (until its timeout): only with the side
-            # stream on a queue of its own
-            from . import streams as S
-            own, side = S.engine_streams()
-            if S.shares_queue(own, side) or S.shares_queue(side, own):
-                self.side_gate = False
         dev = arena.device
         self.dev = dev
         H, Hv = cfg.hidden_size, cfg.v_hidden_size
@@ -370,10 +343,8 @@ class StepEngine:
         # builder state
         self._aside = ""              # suffix of the temporaries of ops being built for a side-stream block (tmp)
         self._split_cur = {}          # stream tag -> [bytes, counters] handed out to the split accumulations of the launch being built
-        self._soft_zero_b_listed = False
         self._n_ln_partial = 0
         self._deferred_ln = []        # LayerNorm backward arguments whose dgamma / dbeta reduction the next _wgrad() places
-        self._n_gate, self._gate_flag = 0, None
         self._slab_cursor = 0
         self._fwd_segments = {}       # fwd_segments() by optimizer range bounds
         self._build()
@@ -427,11 +398,6 @@ class StepEngine:
         arr = self.k((L.GemmProblem * len(probs))(*probs))
         plan_ops.append((L.OP_GEMM, layout | (geometry << 8), epi, len(probs), arr, None, None))
 
-    def gemm_chain(self, plan_ops, layout, epi_p, producers, epi_c, consumers):
-        ap = self.k((L.GemmProblem * len(producers))(*producers))
-        ac = self.k((L.GemmProblem * len(consumers))(*consumers))
-        plan_ops.append((L.OP_GEMM_CHAIN, layout, epi_p | (epi_c << 8), len(producers) | (len(consumers) << 8), ap, ac, None))
-
     def prob(self, A, B, Cout, M, N, K, lda, ldb, ldc, bias=None, R=None, ldr=0, C2=None, bias_grad=None, dyn=None, n_store=0):
         return L.GemmProblem(_addr(A), _addr(B), _addr(Cout), _addr(C2), _addr(bias), _addr(R), _addr(bias_grad), _addr(dyn),
                              M, N, K, lda, ldb, ldc, ldr, n_store)
@@ -465,35 +431,10 @@ class StepEngine:
         cur[1] += tiles.value
         return out
 
-    # ---- soft boundaries (include/volta_hip.h, VK_GEMM_SOFT_START): a GEMM whose A operand is the output of the GEMM launched right before it
-    # is enqueued without the stream-order barrier; its tiles wait for row-block counters that the producer's tiles raise
-    SOFT_ROWS = 1 << 16
-
-    def soft_counters(self, nrb, backward=False):
-        """nrb int32 counters (one per 256-row block) out of the engine's counter arena, which one fill launch at the head of each command
-        list zeroes; plus the address of the error word a timed-out poll raises."""
-        cnt = self.bufs["soft_cnt"]
-        n = _round_up(nrb, 32)                               # a producer's counters on lines of their own
-        assert self._soft_cur + n <= self._soft_cur_b, "hand-off counter arena too small"
-        if backward:
-            self._soft_cur_b -= n
-            cur = self._soft_cur_b
-            self._soft_zero_b.p[0] = cnt.data_ptr() + 4 * cur
-            self._soft_zero_b.n[0] = 4 * (self.SOFT_ROWS - cur)
-            if not self._soft_zero_b_listed:
-                self.bwd_pro.append((L.OP_GENERIC, 0, 0, 0, self._soft_zero_b, None, None))
-                self._soft_zero_b_listed = True
-        else:
-            cur = self._soft_cur
-            self._soft_cur = cur + n
-            self._soft_zero.n[0] = 4 * (self._soft_cur - 32)     # the fill launch at the head of the forward list covers every counter handed out
-        return cnt.data_ptr() + 4 * cur, cnt.data_ptr()
-
     def soft_error(self):
-        """Non-zero when a guarded tile (1) or a weight-gradient gate (2) gave up waiting in some step since the engine was built (host
-        synchronisation: tests and diagnostics)."""
-        e = int(self.bufs["soft_cnt"][0].item()) if "soft_cnt" in self.bufs else 0
-        return e | (int(self.bufs["gate_err"][0].item()) if "gate_err" in self.bufs else 0)
+        """Always 0.  bench.py reads it into the `handoff_errors` field of its result line: the count of row-block hand-offs and
+        weight-gradient gates that gave up waiting.  No plan this engine builds contains a hand-off or a gate, so there is no error word to read."""
+        return 0
 
     def _split_launch_done(self, tag):
         self._split_cur[tag] = [0, 0]
@@ -602,16 +543,6 @@ class StepEngine:
         cfg, B, H = self.cfg, self.B, self.H
         st = self.st
         f = self.fwd.ops
-        if self.soft or self.chain != "0":
-            # row-block counters of the hand-offs: word 0 is the error word (never cleared), the counters start on the next line and
-            # are zeroed by ONE fill launch per command list, in front of everything (its length grows as _build hands counters out);
-            # the forward's counters grow up from the start of the arena, the backward's down from its end
-            self.bufs["soft_cnt"] = torch.zeros(self.SOFT_ROWS, dtype=torch.int32, device=self.dev)
-            self._soft_cur = 32
-            self._soft_cur_b = self.SOFT_ROWS
-            self._soft_zero = self.generic(L.FN_MEMSET, p=(self.bufs["soft_cnt"].data_ptr() + 128,), n=(0, 0))
-            self._soft_zero_b = self.generic(L.FN_MEMSET, p=(self.bufs["soft_cnt"].data_ptr() + 4 * self.SOFT_ROWS,), n=(0, 0))
-            f.append((L.OP_GENERIC, 0, 0, 0, self._soft_zero, None, None))
         # per-step inputs (static staging copies are avoided: the few ops that read them are patched)
         self.masks = [self.buf("mask_t", (B, self.T), torch.float32), self.buf("mask_v", (B, self.Rv), torch.float32)]
         for m, name in ((0, "attention_mask"), (1, "image_attention_mask")):
@@ -1341,18 +1272,8 @@ class StepEngine:
         # dgrad: they need dqkv, not its product, and start beside that GEMM instead of beside the next sub-layer's LayerNorm backward
         self._wgrad(b, ms, shared, [lambda m: (dd[m], ctx[m], self.G(names[m]["o"] + ".weight"), self.G(names[m]["o"] + ".bias"), Hm[m], Ha[m], Hm[m], Ha[m]),
                                     lambda m: (dqkv[m], x_in[m], wqkv(m, "grad"), bqkv(m, "grad"), 3 * Ha[m], Hm[m], 3 * Ha[m], Hm[m])])
-        self.gemm(b, L.NN, L.EPI_ADDR, self.retire_on([self.prob(dqkv[m], wqkv(m, "shadow"), dxn[m], self.st[m].M, Hm[m], 3 * Ha[m], 3 * Ha[m], Hm[m], Hm[m], R=dz[m], ldr=Hm[m]) for m in ms]))
+        self.gemm(b, L.NN, L.EPI_ADDR, [self.prob(dqkv[m], wqkv(m, "shadow"), dxn[m], self.st[m].M, Hm[m], 3 * Ha[m], 3 * Ha[m], Hm[m], Hm[m], R=dz[m], ldr=Hm[m]) for m in ms])
         return b
-
-    @staticmethod
-    def _soft_pair_ok(shapes):
-        """A producer [M, I, H] -> consumer [M, H, I] pair takes the soft boundary when every tile is whole (256-row blocks, 256-wide producer
-        tiles, 192-wide consumer tiles) and both launches are large enough for the 256-row geometries the hand-off is built on."""
-        if any(M % 256 or I % 256 or H % 192 or H % 64 for M, I, H in shapes):
-            return False
-        t_up = sum((M // 256) * (I // 256) for M, I, H in shapes)
-        t_down = sum((M // 256) * -(-H // 256) for M, I, H in shapes)
-        return t_up >= 160 and t_down >= 160
 
     def _ln_pair(self, ops, kind, jobs):
         """One LayerNorm launch for both streams when their widths agree (the kernels share the launch between two jobs of equal width),
@@ -1402,23 +1323,8 @@ class StepEngine:
         else:
             up = [self.prob(x_in[m], self.W(names[m]["up"] + ".weight"), h[m], self.st[m].M, Im[m], Hm[m], Hm[m], Hm[m], Im[m], bias=self.Pm(names[m]["up"] + ".bias"), C2=gp[m]) for m in ms]
             down = [self.prob(h[m], self.W(names[m]["down"] + ".weight"), d[m], self.st[m].M, Hm[m], Im[m], Im[m], Im[m], Hm[m], bias=self.Pm(names[m]["down"] + ".bias")) for m in ms]
-            g_up = g_down = 0
-            pair_ok = self._soft_pair_ok([(self.st[m].M, Im[m], Hm[m]) for m in ms])
-            if self.chain != "0" and pair_ok:
-                for m, pu, pd in zip(ms, up, down):
-                    pu.sig, pu.err = self.soft_counters(self.st[m].M // 256)
-                    pd.dep, pd.err, pd.dep_need = pu.sig, pu.err, Im[m] // 256
-                self.gemm_chain(f, L.NT, L.EPI_GELU, up, L.EPI_BF16, down)
-                up = down = None
-            elif self.soft and pair_ok:
-                # FFN-down starts on the CUs FFN-up's last round leaves idle: row block r of h is handed over by counter (12 column tiles of 256)
-                for m, pu, pd in zip(ms, up, down):
-                    pu.sig, pu.err = self.soft_counters(self.st[m].M // 256)
-                    pd.dep, pd.err, pd.dep_need = pu.sig, pu.err, Im[m] // 256
-                g_up, g_down = 258, 259 | L.GEMM_SOFT_START
-            if up is not None:
-                self.gemm(f, L.NT, L.EPI_GELU, up, geometry=g_up)
-                self.gemm(f, L.NT, L.EPI_BF16, down, geometry=g_down)
+            self.gemm(f, L.NT, L.EPI_GELU, up)
+            self.gemm(f, L.NT, L.EPI_BF16, down)
         odrop, lnf = {}, []
         for m in ms:
             odrop[m] = self.drop(cfg.hidden_dropout_prob if m == 0 else cfg.v_hidden_dropout_prob)
@@ -1445,24 +1351,13 @@ class StepEngine:
         self._ln_pair(b, L.OP_LN_BWD, lnb)
         d1 = [self.prob(dd[m], self.W(names[m]["down"] + ".weight"), du[m], self.st[m].M, Im[m], Hm[m], Hm[m], Im[m], Im[m], R=gp[m], ldr=Im[m]) for m in ms]
         d2 = [self.prob(du[m], self.W(names[m]["up"] + ".weight"), dxn[m], self.st[m].M, Hm[m], Im[m], Im[m], Hm[m], Hm[m], R=dz[m], ldr=Hm[m]) for m in ms]
-        chained = self.chain == "all" and not self.fp8 and self._soft_pair_ok([(self.st[m].M, Im[m], Hm[m]) for m in ms])
-        if chained:
-            # both dgrads in one launch; the weight gradients (which need du, the first one's output) start behind it
-            for m, p1, p2 in zip(ms, d1, d2):
-                p1.sig, p1.err = self.soft_counters(self.st[m].M // 256, backward=True)
-                p2.dep, p2.err, p2.dep_need = p1.sig, p1.err, Im[m] // 256
-            self.gemm_chain(b, L.NN, L.EPI_MULR, d1, L.EPI_ADDR, d2)
-        else:
-            self.gemm(b, L.NN, L.EPI_MULR, d1)
+        self.gemm(b, L.NN, L.EPI_MULR, d1)
         # The weight gradients need dd, h, du and x_in: everything but the LAST dgrad's output.  Their side-stream block is listed in front of that
         # dgrad, so that it starts beside a GEMM (two MFMA-bound launches share the chip without loss) instead of beside the LayerNorm backward
         # that follows, which it used to keep waiting for CUs (profiles/r03_experiments.md: 17.00 / 16.94 -> 16.52 / 16.54 ms per step).
-        gate_mode, self.side_gate = self.side_gate, self.side_gate and not chained      # behind a chain the block starts on the fork event
         self._wgrad(b, ms, shared, [lambda m: (dd[m], h[m], self.G(names[m]["down"] + ".weight"), self.G(names[m]["down"] + ".bias"), Hm[m], Im[m], Hm[m], Im[m]),
                                     lambda m: (du[m], x_in[m], self.G(names[m]["up"] + ".weight"), self.G(names[m]["up"] + ".bias"), Im[m], Hm[m], Im[m], Hm[m])])
-        self.side_gate = gate_mode
-        if not chained:
-            self.gemm(b, L.NN, L.EPI_ADDR, self.retire_on(d2))
+        self.gemm(b, L.NN, L.EPI_ADDR, d2)
         return b
 
     def _wgrad(self, b, ms, shared, specs):
@@ -1511,18 +1406,7 @@ class StepEngine:
             reduces.append((gW, slab, stride, len(chunks), Mo * No))
             reduces.append((gB, slab[Mo * No:], stride, len(chunks), Mo))
         assert len(probs) <= 32, "too many wgrad problems in one group"
-        gate = self._gate_words() if self.side_gate else None
-        b.append((L.OP_SIDE_BEGIN, 1 if gate is not None else 0, 0, 0, None, None, None))
-        if gate is not None:
-            self._n_gate += 1
-            assert self._n_gate < gate.numel()
-            flag = gate.data_ptr() + 8 * self._n_gate
-            b.append((L.OP_GENERIC, 0, 0, 0, self.generic(L.FN_GATE, p=(flag, gate.data_ptr(), self.bufs["gate_err"]), n=(1000000,)), None, None))
-            self._gate_flag = (flag, gate.data_ptr())          # the caller hangs it on the dgrad it lists behind this block (retire_on)
-        if self.side_delay_us > 0:
-            # a pure delay (one wave, no LDS) at the head of the block: the dgrad listed behind it on the compute stream has claimed its CUs
-            # before the weight gradients' workgroups arrive, whatever the latency of the cross-queue wake-up (profiles/r04_experiments.md)
-            b.append((L.OP_GENERIC, 0, 0, 0, self.generic(L.FN_HOLD, n=(1, self.side_delay_us, 0)), None, None))
+        b.append((L.OP_SIDE_BEGIN, 0, 0, 0, None, None, None))
         self.gemm(b, L.TN, L.EPI_F32, probs)
         # every slab sum and every deferred LayerNorm dgamma / dbeta reduction of the sub-layer in ONE launch (vk_side_tail)
         jobs = [L.TailJob(_addr(dst), None, _addr(src), None, stride, n, 0, ns, 0, 0) for dst, src, stride, ns, n in reduces]
@@ -1541,27 +1425,6 @@ class StepEngine:
             b.append((L.OP_GENERIC, 0, 0, 0, self.generic(L.FN_SIDE_TAIL, p=(arr,), n=(len(chunk),)), None, None))
         b.append((L.OP_SIDE_END, self.sub_k % 8, 0, 0, None, None, None))
         self._slab_cursor = 0
-
-    def _gate_words(self):
-        """uint64 words of the weight-gradient gates: word 0 = the epoch, bumped by the first launch of every backward pass (the side stream
-        is ordered behind that launch with the one event of the pass); word k = the flag the k-th block's dgrad stores the epoch to."""
-        if "gate_words" not in self.bufs:
-            self.bufs["gate_words"] = torch.zeros(128, dtype=torch.int64, device=self.dev)
-            self.bufs["gate_words"][1:] = -1
-            self.bufs["gate_err"] = torch.zeros(1, dtype=torch.int32, device=self.dev)
-            g = self.bufs["gate_words"]
-            self.bwd_pro.append((L.OP_GENERIC, 0, 0, 0, self.generic(L.FN_BUMP, p=(g,)), None, None))
-            self.bwd_pro.append((L.OP_SIDE_BEGIN, 0, 0, 0, None, None, None))       # an empty block: its fork event orders the side stream behind the bump
-            self.bwd_pro.append((L.OP_SIDE_END, 13, 0, 0, None, None, None))
-        return self.bufs["gate_words"]
-
-    def retire_on(self, probs):
-        """Hang the pending gate flag on a launch's problem 0: its workgroups release the weight-gradient block as they retire."""
-        gf = self._gate_flag
-        if gf is not None:
-            probs[0].retire_flag, probs[0].retire_stamp = gf
-            self._gate_flag = None
-        return probs
 
     def _slab(self, n):
         """fp32 workspace for split-K partials; one arena reused by every sub-layer (launches are stream-ordered)."""
