@@ -70,13 +70,23 @@ __device__ __forceinline__ float wave_max(float v) {
 // instructions.  The sampling policy of the batch producer (concap.hip) keeps the 10-round default form.
 // The products are written as v_mul_hi_u32 + v_mul_lo_u32 pairs on purpose: the 64-bit form (v_mad_u64_u32) needs
 // aligned register pairs, which pushed the attention forward kernel from 121 to 134 VGPRs (3 instead of 4 waves
-// per SIMD) and made it 25 % slower.
-template <int ROUNDS>
+// per SIMD) and made it 25 % slower.  MUL64 selects the 64-bit form for the kernels that have the registers (the LayerNorm
+// backward: one quarter-rate multiply per product instead of two, 34 instead of 49 VALU instructions per call; the words are the same).
+// Nothing here is hoisted by hand: the rounds are fully unrolled, so with the key and the counter words a caller holds in
+// SGPRs (row, site, 0: see uniform32) the compiler keeps the round keys and the first two rounds' uniform products on the
+// scalar unit and shares them between the calls of a row.
+template <int ROUNDS, bool MUL64 = false>
 __device__ __forceinline__ u32x4 philox4_rounds(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
 #pragma unroll
     for (int i = 0; i < ROUNDS; ++i) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+        uint32_t hi0, lo0, hi1, lo1;
+        if constexpr (MUL64) {
+            const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+            hi0 = (uint32_t)(p0 >> 32); lo0 = (uint32_t)p0; hi1 = (uint32_t)(p1 >> 32); lo1 = (uint32_t)p1;
+        } else {
+            hi0 = __umulhi(0xD2511F53u, c0); lo0 = 0xD2511F53u * c0;
+            hi1 = __umulhi(0xCD9E8D57u, c2); lo1 = 0xCD9E8D57u * c2;
+        }
         const uint32_t n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
         c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
         k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
@@ -97,9 +107,14 @@ struct DropCfg {              // by-value kernel argument
     float scale;              // 1/(1-p)
 };
 
+template <bool MUL64 = false>
 __device__ __forceinline__ u32x4 drop_words(const DropCfg& d, uint64_t seed, uint32_t row, uint32_t c4) {
-    return philox4(c4, row, d.site, 0u, (uint32_t)seed, (uint32_t)(seed >> 32));
+    return philox4_rounds<DROPOUT_PHILOX_ROUNDS, MUL64>(c4, row, d.site, 0u, (uint32_t)seed, (uint32_t)(seed >> 32));
 }
+
+// a value that is the same in every lane of the wave, moved to an SGPR so that what is computed from it runs on the scalar unit
+__device__ __forceinline__ uint32_t uniform32(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+__device__ __forceinline__ uint64_t uniform64(uint64_t v) { return ((uint64_t)uniform32((uint32_t)(v >> 32)) << 32) | uniform32((uint32_t)v); }
 
 // ---- buffer resources (bounds-checked loads: out-of-range reads return 0) ---------------------
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, uint32_t bytes) {

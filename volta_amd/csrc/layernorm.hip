@@ -33,6 +33,16 @@ __device__ __forceinline__ void store4(uint16_t* p, const float (&v)[4]) {
     *(u32x2*)p = u32x2{pack2bf(v[0], v[1]), pack2bf(v[2], v[3])};
 }
 
+// The backward names the global address space in its accesses, so that they are global_load / global_store on a scalar base plus a lane
+// offset: the argument block is copied from the kernel-argument segment as plain words (load_job), so the compiler sees generic pointers,
+// and generic accesses are flat_*: a 64-bit address per lane and both memory counters.
+#define VK_GLOBAL __attribute__((address_space(1)))
+template <typename T> __device__ __forceinline__ VK_GLOBAL T* gptr(void* p) { return (VK_GLOBAL T*)p; }
+template <typename T> __device__ __forceinline__ VK_GLOBAL const T* gptr(const void* p) { return (VK_GLOBAL const T*)p; }
+__device__ __forceinline__ void store4(VK_GLOBAL uint16_t* p, const float (&v)[4]) {
+    *(VK_GLOBAL u32x2*)p = u32x2{pack2bf(v[0], v[1]), pack2bf(v[2], v[3])};
+}
+
 // One launch serves up to two independent jobs (the text and the vision stream of a sub-layer): workgroups
 // [0, nb0) belong to job a0, the rest to job a1.  Each job is a launch-latency-sized problem (30-60 MB), so sharing
 // the launch saves one ramp and fills the chip better than two half-empty grids.
@@ -175,10 +185,12 @@ __global__ __launch_bounds__(LN_THREADS) void ln_bwd_kernel(const JobPair<vk_ln_
     const bool second = (int)blockIdx.x >= nb0;
     const vk_ln_bwd_args a = load_job<vk_ln_bwd_args>(second);
     const int blk = second ? (int)blockIdx.x - nb0 : (int)blockIdx.x;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63, wave = (int)uniform32(threadIdx.x >> 6);      // the wave's rows, and all that follows from them, are scalar
     const int H = a.H;
     const bool drop_on = a.drop.threshold != 0;
-    const uint64_t seed = drop_on ? *a.drop.seed : 0;
+    const uint64_t seed = drop_on ? uniform64(*a.drop.seed) : 0;
+    const VK_GLOBAL uint16_t* const dybase = gptr<uint16_t>(a.dy);
+    const VK_GLOBAL uint16_t* const zbase = gptr<uint16_t>(a.z);
     float pg[NCH][4], pb[NCH][4];
 #pragma unroll
     for (int j = 0; j < NCH; ++j)
@@ -202,13 +214,28 @@ __global__ __launch_bounds__(LN_THREADS) void ln_bwd_kernel(const JobPair<vk_ln_
             dyv[j] = u32x2{0u, 0u};
             zv[j] = u32x2{0u, 0u};
             if (it < RPW && row < Mrows && c < H) {
-                dyv[j] = *(const u32x2*)((const uint16_t*)a.dy + (size_t)row * H + c);
-                zv[j] = *(const u32x2*)((const uint16_t*)a.z + (size_t)row * H + c);
+                dyv[j] = *(const VK_GLOBAL u32x2*)(dybase + (size_t)row * H + c);
+                zv[j] = *(const VK_GLOBAL u32x2*)(zbase + (size_t)row * H + c);
             }
         }
     };
 #pragma unroll
     for (int it = 0; it < PRE; ++it) request(it, rdy[it], rz[it]);
+    // what does not change from row to row is fetched once per wave: gamma (in registers), and the statistics of the wave's rows
+    f32x4 g[NCH];
+    float mean_r[RPW], rstd_r[RPW];
+#pragma unroll
+    for (int j = 0; j < NCH; ++j) {
+        const int c = j * 256 + lane * 4;
+        g[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (c < H) g[j] = *(const VK_GLOBAL f32x4*)(gptr<float>(a.gamma) + c);
+    }
+#pragma unroll
+    for (int it = 0; it < RPW; ++it) {
+        const int row = blk * LN_BWD_ROWS + it * 4 + wave;
+        mean_r[it] = rstd_r[it] = 0.f;
+        if (row < Mrows) { mean_r[it] = gptr<float>(a.mean)[row]; rstd_r[it] = gptr<float>(a.rstd)[row]; }
+    }
 #pragma unroll
     for (int it = 0; it < RPW; ++it) {
         const int row = blk * LN_BWD_ROWS + it * 4 + wave;
@@ -216,7 +243,7 @@ __global__ __launch_bounds__(LN_THREADS) void ln_bwd_kernel(const JobPair<vk_ln_
         uint32_t dsite;
         const uint32_t drow = drop_row(a.seg, a.split_row, row, dsite);
         DropCfg dcfg{a.drop.seed, dsite, a.drop.threshold, a.drop.scale};
-        const float mean = a.mean[row], rstd = a.rstd[row];
+        const float mean = mean_r[it], rstd = rstd_r[it];
         float xh[NCH][4], gh[NCH][4];
         uint32_t keep[NCH];              // bit r: element r of the chunk survives the dropout (4 bits instead of the 4 Philox words)
         float s1 = 0.f, s2 = 0.f;
@@ -231,10 +258,9 @@ __global__ __launch_bounds__(LN_THREADS) void ln_bwd_kernel(const JobPair<vk_ln_
                 const float zv[4] = {bf2f(z2[0] & 0xFFFF), bf2f(z2[0] >> 16), bf2f(z2[1] & 0xFFFF), bf2f(z2[1] >> 16)};
                 keep[j] = 0xFu;
                 if (drop_on) {
-                    const u32x4 w = drop_words(dcfg, seed, drow, (uint32_t)(c >> 2));
+                    const u32x4 w = drop_words<true>(dcfg, seed, drow, (uint32_t)(c >> 2));
                     keep[j] = (w[0] >= a.drop.threshold ? 1u : 0u) | (w[1] >= a.drop.threshold ? 2u : 0u) | (w[2] >= a.drop.threshold ? 4u : 0u) | (w[3] >= a.drop.threshold ? 8u : 0u);
                 }
-                const f32x4 g = *(const f32x4*)(a.gamma + c);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     float gy = dv[r] * a.out_scale;
@@ -242,7 +268,7 @@ __global__ __launch_bounds__(LN_THREADS) void ln_bwd_kernel(const JobPair<vk_ln_
                     const float xv = (zv[r] - mean) * rstd;
                     pg[j][r] += gy * xv;
                     pb[j][r] += gy;
-                    const float gx = gy * g[r];
+                    const float gx = gy * g[j][r];
                     xh[j][r] = xv;
                     gh[j][r] = gx;
                     s1 += gx;
@@ -254,8 +280,8 @@ __global__ __launch_bounds__(LN_THREADS) void ln_bwd_kernel(const JobPair<vk_ln_
         s1 = wave_sum(s1) / (float)H;
         s2 = wave_sum(s2) / (float)H;
         if (stamping && it == 0) stamps[(size_t)blockIdx.x * 4 + 1] = __builtin_amdgcn_s_memrealtime();
-        uint16_t* dz = (uint16_t*)a.dz + (size_t)row * H;
-        uint16_t* dd = a.dd ? (uint16_t*)a.dd + (size_t)row * H : nullptr;
+        VK_GLOBAL uint16_t* dz = gptr<uint16_t>(a.dz) + (size_t)row * H;
+        VK_GLOBAL uint16_t* dd = a.dd ? gptr<uint16_t>(a.dd) + (size_t)row * H : nullptr;
 #pragma unroll
         for (int j = 0; j < NCH; ++j) {
             const int c = j * 256 + lane * 4;
@@ -284,7 +310,7 @@ __global__ __launch_bounds__(LN_THREADS) void ln_bwd_kernel(const JobPair<vk_ln_
             red[wave][1][j * 256 + lane * 4 + r] = pb[j][r];
         }
     __syncthreads();
-    float* out = a.partial + (size_t)blk * 2 * H;
+    VK_GLOBAL float* out = gptr<float>(a.partial) + (size_t)blk * 2 * H;
     for (int i = threadIdx.x; i < 2 * NCH * 256; i += LN_THREADS) {
         const int which = i / (NCH * 256), c = i - which * NCH * 256;
         if (c < H) out[which * H + c] = red[0][which][c] + red[1][which][c] + red[2][which][c] + red[3][which][c];
