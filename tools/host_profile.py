@@ -14,5 +14,5 @@ pr.disable()
 s = io.StringIO()
 st = pstats.Stats(pr, stream=s)
 st.sort_stats("cumulative").print_callees(r"bench.py:\d+\(step\)")
-st.print_callees(r"_engine_backward|_engine_forward|clip_grad_norm_|optimization.py:\d+\(step\)|zero_grad|Plan.run|engine.py:\d+\(run\)|prepare_step|bind_inputs|modeling.py:\d+\(forward\)")
+st.print_callees(r"_engine_backward|_engine_forward|clip_grad_norm_|optimization.py:\d+\(step\)|zero_grad|Plan.run|plan.py:\d+\(run\)|prepare_step|bind_inputs|modeling.py:\d+\(forward\)")
 print(s.getvalue())

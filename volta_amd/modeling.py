@@ -1,6 +1,6 @@
 """Drop-in model classes: same constructor / forward signatures, parameter names and error behaviour as the
 reference's `BertModel` / `BertForVLPreTraining` (volta/encoders.py:918-1114, volta/utils.py:250-360), with the
-whole forward + backward dispatched to the HIP engine (volta_amd/engine.py).  There is no eager / CPU
+whole forward + backward dispatched to the HIP engine (volta_amd/engine/).  There is no eager / CPU
 fallback: without a GPU and libvolta_hip.so the forward raises.
 
 Differences a caller can observe, all deliberate:
@@ -677,7 +677,7 @@ def _attention_maps(config, eng, requested):
 # ======================================================================================== downstream tasks
 class SimpleClassifier(nn.Module):
     """Linear -> GELU -> LayerNorm -> Linear (volta/encoders.py:787-815): the parameter container with the reference's names; the arithmetic
-    runs on the HIP engine (engine.py:_heads_tasks), `forward` is kept for reference use on CPU copies only."""
+    runs on the HIP engine (engine/heads.py:_heads_tasks), `forward` is kept for reference use on CPU copies only."""
 
     def __init__(self, in_dim, hid_dim, out_dim, dropout_prob=0.0):
         super().__init__()

@@ -1,6 +1,6 @@
 """Parameter containers named and shaped exactly like the reference's module tree, so that `state_dict()`s
 interchange with volta checkpoints.  They hold weights only -- the arithmetic runs in the
-HIP engine (volta_amd/engine.py) -- and are generated from small declarative specs instead of one class
+HIP engine (volta_amd/engine/) -- and are generated from small declarative specs instead of one class
 per layer.  Reference sites: volta/embeddings.py:39-53,127-160,184-238,304-334,401-431 (embeddings),
 volta/encoders.py:163-218,361-396,452-484,504-539 (gated sub-layers), :596-637 (poolers), :643-764 (heads).
 """

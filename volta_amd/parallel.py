@@ -31,7 +31,7 @@ import torch
 import torch.distributed as dist
 from torch import nn
 
-SLOT = 1024        # parameter slots of the flat arenas are aligned to this many elements (engine.CHUNK)
+SLOT = 1024        # parameter slots of the flat arenas are aligned to this many elements (engine.CHUNK, engine/arena.py)
 
 
 def plan_buckets(spans, ready, n_stages, cap_bytes, elem_bytes=4, pad_to=1, total=None):

@@ -12,7 +12,7 @@ Precision: `projection_dtype="fp8"` runs the Q|K|V and feed-forward projections 
 from the model after `set_projection_dtype("fp8")` -- the fp8 model's scores and ranks, not the bf16 model's.  "bf16" asks for the bf16
 projections explicitly; None is bf16 too, but refuses a model whose own switch was left on fp8.  Where a prefix ends in a sub-layer, the
 e4m3 copy its last LayerNorm wrote (and the copy's row scales) is kept in the handle and gathered per pair, so that the suffix's first
-projection reads the bits the whole model reads there (`engine.pair_segments`).
+projection reads the bits the whole model reads there (`engine.pair_segments`, engine/builder.py).
 
     scorer = RetrievalScorer(model, task_id="TASK8", pair_chunk=1000)
     caps = scorer.encode_captions(input_ids, segment_ids, input_mask)      # [Nc, T] each, on the GPU
