@@ -68,7 +68,8 @@ typedef struct vk_gemm_problem {
     void* C;
     void* C2;              /* VK_EPI_GELU: derivative output, same ld as C */
     const float* bias;     /* [N] fp32 or NULL */
-    const void* R;         /* bf16 [M, ldr] for MULR / ADDR */
+    const void* R;         /* bf16 [M, ldr] for MULR / ADDR; ldr even and >= N: R is read 4 bytes at a time under a bounds check, and with an odd
+                              N the partner of R[M-1][N-1] (the pad element R[M-1][N]) is read with it -- whole rows of ldr elements must exist */
     float* bias_grad;      /* TN only: if non-NULL receives sum over the K rows of A -> [M] fp32 */
     const int32_t* dyn;    /* see above */
     int32_t M, N, K;

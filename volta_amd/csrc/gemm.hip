@@ -262,6 +262,7 @@ static int gemm_dispatch(int layout, int epilogue, const vk_gemm_problem* probs,
             return set_error("vk_gemm_grouped: K=%d needs lda padded to a multiple of 64", q.K);
         if (layout != VK_TN && q.bias_grad) return set_error("vk_gemm_grouped: bias_grad is a TN (wgrad) feature");
         if ((epilogue == VK_EPI_MULR || epilogue == VK_EPI_ADDR) && !q.R) return set_error("vk_gemm_grouped: R missing");
+        if ((epilogue == VK_EPI_MULR || epilogue == VK_EPI_ADDR) && ((q.ldr & 1) || q.ldr < q.N)) return set_error("vk_gemm_grouped: ldr must be even and >= N (got %d, N %d)", q.ldr, q.N);
         if (epilogue == VK_EPI_GELU && !q.C2) return set_error("vk_gemm_grouped: C2 missing");
         any_dyn |= q.dyn != nullptr;
         any_split |= q.nparts > 1;

@@ -259,7 +259,9 @@ __device__ __forceinline__ void gemm_epilogue(const KProb& P, f32x4 (&acc)[TI][T
             for (int r = 0; r < 4; ++r)
                 bv[j][r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rb, (uint32_t)(n_base + j * 16 + gq * 4 + r) * 4u, 0, 0));
     }
-    const __amdgpu_buffer_rsrc_t rr = make_rsrc(P.R, (USE_R && Mout > 0) ? (uint32_t)(((uint32_t)(Mout - 1) * P.ldr + N) * 2u) : 0u);
+    // (R's rows end on an even element count inside ldr, as the operands' do (even_up): with an odd N the dword that holds R[Mout-1][N-1] would
+    // otherwise end past the extent and read as zero -- the last element of the last row lost its residual / multiplier; ldr is even, gemm_dispatch)
+    const __amdgpu_buffer_rsrc_t rr = make_rsrc(P.R, (USE_R && Mout > 0) ? (uint32_t)(((uint32_t)(Mout - 1) * P.ldr + even_up(N, P.ldr)) * 2u) : 0u);
     const __amdgpu_buffer_rsrc_t rc = make_rsrc(P.C, (EPI == VK_EPI_F32_ACC && Mout > 0) ? (uint32_t)(((uint32_t)(Mout - 1) * P.ldc + nlim) * 4u) : 0u);
 
 #pragma unroll
@@ -299,8 +301,11 @@ __device__ __forceinline__ void gemm_epilogue(const KProb& P, f32x4 (&acc)[TI][T
 #pragma unroll
                 for (int r = 0; r < 4; ++r) if (n + r >= N) v[r] = 0.f;
                 if (EPI == VK_EPI_F32_ACC) {
+                    // (the whole vector is cast: __builtin_bit_cast(float, cv[j][r]) takes the vector ELEMENT as an lvalue and compiled to element 0
+                    // for every r -- the ragged path added C[m][n] of a 4-group's first column to all four columns)
+                    const f32x4 cprev = __builtin_bit_cast(f32x4, cv[j]);
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) v[r] += __builtin_bit_cast(float, cv[j][r]);
+                    for (int r = 0; r < 4; ++r) v[r] += cprev[r];
                 }
                 if (!row_ok || n >= nlim) continue;
                 float* c = (float*)P.C + off;

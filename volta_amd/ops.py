@@ -37,7 +37,8 @@ def gemm_problem(A, B, Cout, layout, M, N, K, bias=None, R=None, C2=None, bias_g
     if R is not None:
         _bf16(R)
         ldr = ldr if ldr is not None else R.stride(-2)
-        assert (M - 1) * ldr + N <= R.untyped_storage().nbytes() // 2 - R.storage_offset()
+        assert ldr % 2 == 0 and ldr >= N, "ldr must be even and >= N"
+        assert (M - 1) * ldr + min((N + 1) & ~1, ldr) <= R.untyped_storage().nbytes() // 2 - R.storage_offset()      # rows end on an even count (gemm_epilogue)
     if bias_grad is not None:
         assert bias_grad.dtype == torch.float32 and bias_grad.numel() >= M
     if dyn is not None:
