@@ -123,6 +123,9 @@ int vk_gemm_grouped(int layout, int epilogue, const vk_gemm_problem* probs, int 
  * dispatched in enqueue order -- tools/micro/dispatch_order.hip -- so a polling workgroup never holds a CU that a producer still needs.) */
 #define VK_GEMM_SOFT_START 0x4000
 int vk_gemm_grouped_ex(int layout, int epilogue, const vk_gemm_problem* probs, int nprob, int geometry, vk_stream_t s);
+/* The geometry code vk_gemm_grouped picks for this group (host-side: reads M, N, n_store and dyn of the problems only).  A launch
+   of a subset of the group with this code runs the kernels the whole group would have run: the step engine's pruned backward lists. */
+int vk_gemm_geometry(int layout, int epilogue, const vk_gemm_problem* probs, int nprob);
 /* Chain: a producer group and the consumer group that reads its outputs in ONE persistent launch (the reference's BertGatedIntermediate ->
  * BertGatedOutput pair, volta/encoders.py:486-501 -> 541-566, and its backward: FFN-down dgrad x gelu' -> FFN-up dgrad).  Producers run on
  * 256 x 256 tiles with epilogue `epi_p` and signal row blocks (`sig`); consumers run on 256 x 192 tiles with epilogue `epi_c`, each reads
@@ -201,9 +204,10 @@ typedef struct vk_ln_bwd_args {
     const float* mean;
     const float* rstd;
     const float* gamma;
-    void* dz;              /* bf16 [M, H]: gradient w.r.t. z (= gradient of the residual branch and of addvec rows) */
+    void* dz;              /* bf16 [M, H]: gradient w.r.t. z (= gradient of the residual branch and of addvec rows); NULL: not needed */
     void* dd;              /* bf16 [M, H]: gradient w.r.t. d (pre-dropout mask re-applied); NULL: not needed */
-    float* partial;        /* workspace fp32 [vk_ln_bwd_partial_rows(M), 2, H] */
+    float* partial;        /* workspace fp32 [vk_ln_bwd_partial_rows(M), 2, H]; NULL: gamma and beta are frozen -- no records, dgamma / dbeta
+                              ignored, the launch takes the instantiation without column sums (dz / dd bit-equal to the full one's) */
     float* dgamma;         /* [H]  column sums over the job's rows: 0 for a job without rows (M <= 0 or *dyn == 0) */
     float* dbeta;          /* [H] */
     const int32_t* dyn;
@@ -218,9 +222,11 @@ typedef struct vk_ln_bwd_args {
 } vk_ln_bwd_args;
 int vk_ln_bwd_partial_rows(int M);
 int vk_ln_bwd(const vk_ln_bwd_args* a, vk_stream_t s);
+/* A pair with one `partial` NULL and one not is issued as two launches. */
 int vk_ln_bwd_pair(const vk_ln_bwd_args* a, const vk_ln_bwd_args* b, vk_stream_t s);
 /* dgamma / dbeta from the per-workgroup partial records of a vk_ln_bwd issued with accumulate bit 1 set: off the
-   critical path of the backward pass (the parameters' gradients are only needed by the optimizer / all-reduce). */
+   critical path of the backward pass (the parameters' gradients are only needed by the optimizer / all-reduce).  An error for a job
+   whose `partial` is NULL. */
 int vk_ln_bwd_finalize(const vk_ln_bwd_args* a, vk_stream_t s);
 
 /* ------------------------------------------------------------------------------------------------

@@ -247,6 +247,34 @@ static int total_tiles(const vk_gemm_problem* probs, int nprob, int epilogue, in
 
 }  // namespace vk
 
+// The geometry code a launch without one gets (the comment in gemm_dispatch says what the codes are).
+static int heuristic_edge(int layout, int epilogue, const vk_gemm_problem* probs, int nprob, bool any_dyn) {
+    using namespace vk;
+    int edge;
+    const int t256 = total_tiles(probs, nprob, epilogue, 256, 256), t192 = total_tiles(probs, nprob, epilogue, 256, 192);
+    if (t256 < (layout == VK_TN ? g_min_tiles256_tn : g_min_tiles256)) edge = 128;
+    else {
+        const double c256 = (double)((t256 + 255) / 256) * 256.0, c192 = (double)((t192 + 255) / 256) * 192.0;
+        edge = c192 < 0.97 * c256 ? 259 : 258;
+    }
+    if (edge == 128 && layout == VK_NT && !any_dyn) {
+        // launches too small for 256-row tiles, K-contiguous operands: the 4-wave ring kernel with 128 x 128 tiles (five K-steps in flight,
+        // one workgroup per CU) instead of the double-buffered one -- text-only FFN-down 56.5 -> 48.1 us, attention output 22.0 -> 19.0
+        // (profiles/r03_gemm_shapes.txt); the transposed-operand layouts measured no better on it
+        bool deep = true;
+        for (int i = 0; i < nprob; ++i) deep &= probs[i].M >= 1024 && probs[i].K >= 512;
+        if (deep) edge = 262;
+    }
+    return edge;
+}
+
+extern "C" int vk_gemm_geometry(int layout, int epilogue, const vk_gemm_problem* probs, int nprob) {
+    if (nprob < 1 || nprob > VK_GEMM_MAX_GROUP) return 0;
+    bool any_dyn = false;
+    for (int i = 0; i < nprob; ++i) any_dyn |= probs[i].dyn != nullptr;
+    return heuristic_edge(layout, epilogue, probs, nprob, any_dyn);
+}
+
 static int gemm_dispatch(int layout, int epilogue, const vk_gemm_problem* probs, int nprob, int geometry, vk_stream_t stream) {
     using namespace vk;
     if (nprob < 1 || nprob > VK_GEMM_MAX_GROUP) return set_error("vk_gemm_grouped: nprob %d out of range", nprob);
@@ -307,22 +335,7 @@ static int gemm_dispatch(int layout, int epilogue, const vk_gemm_problem* probs,
     for (int i = 0; i < nprob; ++i) any_handoff |= probs[i].sig != nullptr || probs[i].dep != nullptr;
     const int walk = geometry & (VK_GEMM_PERSISTENT | VK_GEMM_ONE_TILE_PER_WG);
     int edge = geometry & 0xFFF;
-    if (edge == 0) {
-        const int t256 = total_tiles(probs, nprob, epilogue, 256, 256), t192 = total_tiles(probs, nprob, epilogue, 256, 192);
-        if (t256 < (layout == VK_TN ? g_min_tiles256_tn : g_min_tiles256)) edge = 128;
-        else {
-            const double c256 = (double)((t256 + 255) / 256) * 256.0, c192 = (double)((t192 + 255) / 256) * 192.0;
-            edge = c192 < 0.97 * c256 ? 259 : 258;
-        }
-    }
-    if (edge == 128 && (geometry & 0xFFF) == 0 && layout == VK_NT && !any_dyn) {
-        // launches too small for 256-row tiles, K-contiguous operands: the 4-wave ring kernel with 128 x 128 tiles (five K-steps in flight,
-        // one workgroup per CU) instead of the double-buffered one -- text-only FFN-down 56.5 -> 48.1 us, attention output 22.0 -> 19.0
-        // (profiles/r03_gemm_shapes.txt); the transposed-operand layouts measured no better on it
-        bool deep = true;
-        for (int i = 0; i < nprob; ++i) deep &= probs[i].M >= 1024 && probs[i].K >= 512;
-        if (deep) edge = 262;
-    }
+    if (edge == 0) edge = heuristic_edge(layout, epilogue, probs, nprob, any_dyn);
     if (edge == 256 || edge == 258 || edge == 259 || edge == 260 || edge == 261 || edge == 262) {
         for (int i = 0; i < nprob; ++i) {
             const vk_gemm_problem& q = probs[i];

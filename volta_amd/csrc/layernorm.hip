@@ -169,9 +169,12 @@ __global__ __launch_bounds__(LN_THREADS) void ln_fwd_kernel(const JobPair<vk_ln_
 
 // `stamps` (study builds; NULL in the shipped library's launches): per workgroup four s_memrealtime readings (100 MHz) -- entry, first
 // row's statistics done (= its operands arrived), last row stored, record written -- into a buffer no other code reads (tools/stamp_ln.py).
-template <int NCH>
-__global__ __launch_bounds__(LN_THREADS) void ln_bwd_kernel(const JobPair<vk_ln_bwd_args> jp, unsigned long long* const stamps) {
-    __shared__ float red[4][2][NCH * 256];
+// The body of both backward kernels.  PARAMS = false (ln_bwd_dx_kernel) serves jobs whose gamma and beta are frozen (`partial` NULL in
+// both jobs of the launch): no column accumulators, no LDS record, no barrier.  The row arithmetic is the same code, so dz / dd carry the
+// same bits.  `dz` NULL skips that store, as `dd` NULL does: a stream whose input gradient nobody reads.
+template <int NCH, bool PARAMS>
+__device__ __forceinline__ void ln_bwd_body(const JobPair<vk_ln_bwd_args> jp, unsigned long long* const stamps) {
+    __shared__ float red[PARAMS ? 4 : 1][2][PARAMS ? NCH * 256 : 1];
     const bool stamping = stamps != nullptr && threadIdx.x == 0;
 #ifdef VK_STUDY
     if (jp.stagger > 0) {          // experiment: de-phase the workgroups of the single resident round (measured: no gain)
@@ -191,11 +194,13 @@ __global__ __launch_bounds__(LN_THREADS) void ln_bwd_kernel(const JobPair<vk_ln_
     const uint64_t seed = drop_on ? uniform64(*a.drop.seed) : 0;
     const VK_GLOBAL uint16_t* const dybase = gptr<uint16_t>(a.dy);
     const VK_GLOBAL uint16_t* const zbase = gptr<uint16_t>(a.z);
-    float pg[NCH][4], pb[NCH][4];
+    float pg[PARAMS ? NCH : 1][4], pb[PARAMS ? NCH : 1][4];
+    if constexpr (PARAMS) {
 #pragma unroll
-    for (int j = 0; j < NCH; ++j)
+        for (int j = 0; j < NCH; ++j)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) pg[j][r] = pb[j][r] = 0.f;
+            for (int r = 0; r < 4; ++r) pg[j][r] = pb[j][r] = 0.f;
+    }
 
     const int Mrows = a.dyn ? min(*a.dyn, a.M) : a.M;
     // Each wave owns LN_BWD_ROWS / 4 rows; the bf16 inputs of ALL of them are requested up front (raw 8-byte
@@ -266,8 +271,10 @@ __global__ __launch_bounds__(LN_THREADS) void ln_bwd_kernel(const JobPair<vk_ln_
                     float gy = dv[r] * a.out_scale;
                     if (drop_on && a.post) gy = ((keep[j] >> r) & 1u) ? gy * a.drop.scale : 0.f;
                     const float xv = (zv[r] - mean) * rstd;
-                    pg[j][r] += gy * xv;
-                    pb[j][r] += gy;
+                    if constexpr (PARAMS) {
+                        pg[j][r] += gy * xv;
+                        pb[j][r] += gy;
+                    }
                     const float gx = gy * g[j][r];
                     xh[j][r] = xv;
                     gh[j][r] = gx;
@@ -280,7 +287,7 @@ __global__ __launch_bounds__(LN_THREADS) void ln_bwd_kernel(const JobPair<vk_ln_
         s1 = wave_sum(s1) / (float)H;
         s2 = wave_sum(s2) / (float)H;
         if (stamping && it == 0) stamps[(size_t)blockIdx.x * 4 + 1] = __builtin_amdgcn_s_memrealtime();
-        VK_GLOBAL uint16_t* dz = gptr<uint16_t>(a.dz) + (size_t)row * H;
+        VK_GLOBAL uint16_t* dz = a.dz ? gptr<uint16_t>(a.dz) + (size_t)row * H : nullptr;
         VK_GLOBAL uint16_t* dd = a.dd ? gptr<uint16_t>(a.dd) + (size_t)row * H : nullptr;
 #pragma unroll
         for (int j = 0; j < NCH; ++j) {
@@ -289,7 +296,7 @@ __global__ __launch_bounds__(LN_THREADS) void ln_bwd_kernel(const JobPair<vk_ln_
                 float o[4];
 #pragma unroll
                 for (int r = 0; r < 4; ++r) o[r] = rstd * (gh[j][r] - s1 - xh[j][r] * s2);
-                store4(dz + c, o);
+                if (dz) store4(dz + c, o);
                 if (dd) {
                     if (drop_on && !a.post) {
 #pragma unroll
@@ -301,21 +308,33 @@ __global__ __launch_bounds__(LN_THREADS) void ln_bwd_kernel(const JobPair<vk_ln_
         }
     }
     if (stamping) stamps[(size_t)blockIdx.x * 4 + 2] = __builtin_amdgcn_s_memrealtime();
-    // reduce the four waves' column partials, one [2][H] record per workgroup
+    if constexpr (PARAMS) {
+        // reduce the four waves' column partials, one [2][H] record per workgroup
 #pragma unroll
-    for (int j = 0; j < NCH; ++j)
+        for (int j = 0; j < NCH; ++j)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            red[wave][0][j * 256 + lane * 4 + r] = pg[j][r];
-            red[wave][1][j * 256 + lane * 4 + r] = pb[j][r];
+            for (int r = 0; r < 4; ++r) {
+                red[wave][0][j * 256 + lane * 4 + r] = pg[j][r];
+                red[wave][1][j * 256 + lane * 4 + r] = pb[j][r];
+            }
+        __syncthreads();
+        VK_GLOBAL float* out = gptr<float>(a.partial) + (size_t)blk * 2 * H;
+        for (int i = threadIdx.x; i < 2 * NCH * 256; i += LN_THREADS) {
+            const int which = i / (NCH * 256), c = i - which * NCH * 256;
+            if (c < H) out[which * H + c] = red[0][which][c] + red[1][which][c] + red[2][which][c] + red[3][which][c];
         }
-    __syncthreads();
-    VK_GLOBAL float* out = gptr<float>(a.partial) + (size_t)blk * 2 * H;
-    for (int i = threadIdx.x; i < 2 * NCH * 256; i += LN_THREADS) {
-        const int which = i / (NCH * 256), c = i - which * NCH * 256;
-        if (c < H) out[which * H + c] = red[0][which][c] + red[1][which][c] + red[2][which][c] + red[3][which][c];
     }
     if (stamping) stamps[(size_t)blockIdx.x * 4 + 3] = __builtin_amdgcn_s_memrealtime();
+}
+
+template <int NCH>
+__global__ __launch_bounds__(LN_THREADS) void ln_bwd_kernel(const JobPair<vk_ln_bwd_args> jp, unsigned long long* const stamps) {
+    ln_bwd_body<NCH, true>(jp, stamps);
+}
+
+template <int NCH>
+__global__ __launch_bounds__(LN_THREADS) void ln_bwd_dx_kernel(const JobPair<vk_ln_bwd_args> jp, unsigned long long* const stamps) {
+    ln_bwd_body<NCH, false>(jp, stamps);
 }
 
 // column sums of the per-workgroup partial records: 64 columns x 16 row groups per workgroup
@@ -390,6 +409,15 @@ extern "C" int vk_ln_bwd_pair(const vk_ln_bwd_args* a, const vk_ln_bwd_args* b, 
     using namespace vk;
     if (ln_check(a->H, 2048, "vk_ln_bwd")) return -1;
     if (b && (b->H != a->H || a->dyn || b->dyn)) return set_error("vk_ln_bwd_pair: both jobs need the same H and static row counts");
+    // `partial` NULL: the job's gamma and beta are frozen -- dgamma / dbeta are ignored and the launch takes the instantiation without
+    // the column sums.  A mixed pair is two launches: the full instantiation would hold the frozen job's workgroups to its own
+    // registers, LDS and barrier ("Frozen parameters"), and the records of the other job are those of a launch alone.
+    if (b && !a->partial != !b->partial) {
+        if (vk_ln_bwd_pair(a, nullptr, stream)) return -1;
+        return vk_ln_bwd_pair(b, nullptr, stream);
+    }
+    const bool params = a->partial != nullptr;
+    if (!params && !a->dz && !a->dd && (!b || (!b->dz && !b->dd))) return 0;      // nothing asked for
     const int nb0 = a->M > 0 ? vk_ln_bwd_partial_rows(a->M) : 0, nb1 = (b && b->M > 0) ? vk_ln_bwd_partial_rows(b->M) : 0;
     const int nch = (a->H + 255) / 256;
     dim3 grid(nb0 + nb1), block(LN_THREADS);
@@ -399,7 +427,7 @@ extern "C" int vk_ln_bwd_pair(const vk_ln_bwd_args* a, const vk_ln_bwd_args* b, 
     jp.job[1] = b ? *b : *a;
     jp.nb0 = nb0;
     jp.stagger = g_ln_stagger; jp.stagger_mod = g_ln_stagger_mod;
-    if (nb0 + nb1) switch (nch) {
+    if (nb0 + nb1 && params) switch (nch) {
         case 1: hipLaunchKernelGGL(ln_bwd_kernel<1>, grid, block, 0, s, jp, g_ln_stamps); break;
         case 2: hipLaunchKernelGGL(ln_bwd_kernel<2>, grid, block, 0, s, jp, g_ln_stamps); break;
         case 3: hipLaunchKernelGGL(ln_bwd_kernel<3>, grid, block, 0, s, jp, g_ln_stamps); break;
@@ -407,6 +435,15 @@ extern "C" int vk_ln_bwd_pair(const vk_ln_bwd_args* a, const vk_ln_bwd_args* b, 
         case 5: case 6: hipLaunchKernelGGL(ln_bwd_kernel<6>, grid, block, 0, s, jp, g_ln_stamps); break;      // clf_hidden_size 1536 (task classifiers)
         default: hipLaunchKernelGGL(ln_bwd_kernel<8>, grid, block, 0, s, jp, g_ln_stamps); break;
     }
+    if (nb0 + nb1 && !params) switch (nch) {       // the same table, the instantiations without column sums
+        case 1: hipLaunchKernelGGL(ln_bwd_dx_kernel<1>, grid, block, 0, s, jp, g_ln_stamps); break;
+        case 2: hipLaunchKernelGGL(ln_bwd_dx_kernel<2>, grid, block, 0, s, jp, g_ln_stamps); break;
+        case 3: hipLaunchKernelGGL(ln_bwd_dx_kernel<3>, grid, block, 0, s, jp, g_ln_stamps); break;
+        case 4: hipLaunchKernelGGL(ln_bwd_dx_kernel<4>, grid, block, 0, s, jp, g_ln_stamps); break;
+        case 5: case 6: hipLaunchKernelGGL(ln_bwd_dx_kernel<6>, grid, block, 0, s, jp, g_ln_stamps); break;
+        default: hipLaunchKernelGGL(ln_bwd_dx_kernel<8>, grid, block, 0, s, jp, g_ln_stamps); break;
+    }
+    if (!params) return check_launch("vk_ln_bwd");
     // a job without rows has no records: its finalize assigns the empty sum, 0 (nothing to do when it would only add it)
     if ((nb0 || !(a->accumulate & 1)) && !(a->accumulate & 2)) ln_finalize_launch(a, s);
     if (b && (nb1 || !(b->accumulate & 1)) && !(b->accumulate & 2)) ln_finalize_launch(b, s);
@@ -416,6 +453,7 @@ extern "C" int vk_ln_bwd_pair(const vk_ln_bwd_args* a, const vk_ln_bwd_args* b, 
 extern "C" int vk_ln_bwd(const vk_ln_bwd_args* a, vk_stream_t stream) { return vk_ln_bwd_pair(a, nullptr, stream); }
 
 extern "C" int vk_ln_bwd_finalize(const vk_ln_bwd_args* a, vk_stream_t stream) {
+    if (!a->partial) return vk::set_error("vk_ln_bwd_finalize: the job has no partial records (partial NULL: gamma and beta frozen)");
     if (a->M <= 0 && (a->accumulate & 1)) return 0;
     ln_finalize_launch(a, (hipStream_t)stream);
     return vk::check_launch("vk_ln_bwd_finalize");

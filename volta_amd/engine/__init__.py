@@ -14,6 +14,6 @@ Dropout sites are numbered in the order of the reference's forward (embeddings; 
 vv, vt probabilities, text output, vision output; pooled) -- the contract the mask-replay tests rely on.
 """
 from .arena import CHUNK, NO_DECAY, ParamArena
-from .builder import StepEngine, Stream, pair_segments, wide_geometry
+from .builder import StepEngine, Stream, pair_segments, wide_geometry, canonical_frozen, frozen_blocks
 from .heads import VIS_TARGET_WIDTH
 from .plan import Plan

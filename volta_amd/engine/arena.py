@@ -64,6 +64,8 @@ class ParamArena:
         self.fp8_epoch = -1
         self._plist = self._gviews = None       # param_list() / grad_views(), built on first use
         self.opt_pending = None         # (range bounds, events) of a pipelined optimizer step still in flight (optimization.py)
+        self.frozen_memo = None         # (requires_grad pattern, its pruning decision) of the last forward (modeling._frozen_signature)
+        self.grad_plan = None           # weak reference to the plan whose backward wrote `grad` last (modeling._backward_begin)
 
     def view(self, name, which="master"):
         buf = getattr(self, which)

@@ -1,6 +1,7 @@
 """StepEngine: the buffers and the forward / backward command lists of one shape, built once and replayed every step."""
 import ctypes as C
 import os
+import re
 
 import torch
 
@@ -10,8 +11,41 @@ from ..modules import sublayer_schedule
 from .arena import CHUNK
 from .embeddings import EmbeddingBuilders
 from .heads import HeadBuilders
-from .plan import (EV_IMAGE_EMB_BWD, EV_IMAGE_EMB_FWD, EV_WGRAD_RING, NODROP, Plan, _addr, _mk_segs, _round_up, op, side_begin, side_end, wait_side)
+from .plan import (EV_DECODER_WGRAD, EV_IMAGE_EMB_BWD, EV_IMAGE_EMB_FWD, EV_WGRAD_RING, NODROP, Plan, _addr, _mk_segs, _round_up, op, side_begin, side_end, wait_side)
 from .sublayers import SublayerBuilders
+
+
+def frozen_blocks(arena, heads="pretrain"):
+    """The blocks a backward list is pruned by: [[arena names]].  A block's gradient ops are dropped when every parameter of it is frozen
+    and stay as they are otherwise.  One block each: the weight and bias of a Linear (one TN problem writes both); the six Q|K|V tensors
+    of an attention sub-layer and modality (one [3 Ha, Hm] product); gamma and beta of a LayerNorm; everything under one embedding
+    prefix (one backward; VisualBERT, VL-BERT and UNITER embed both modalities under one prefix).  The tied LM decoder of the pre-training
+    heads writes the word table's gradient and the decoder bias in one product: there (word table, decoder bias) is a block too, and
+    the word table's gradient is left alone only when both blocks it belongs to are frozen."""
+    blocks = {}
+    if heads == "pretrain":
+        blocks["decoder"] = ["bert.embeddings.word_embeddings.weight"]
+    for name in arena.params:
+        m = re.match(r"bert\.(v_)?embeddings\.", name)
+        if m:
+            key = m.group(0)
+        elif heads == "pretrain" and name == "cls.predictions.bias":
+            key = "decoder"
+        else:
+            key = re.sub(r"\.attention_self\.(v_)?(query|key|value)\.(weight|bias)$", r".attention_self.\1qkv", name)
+            if key == name:
+                key = name.rsplit(".", 1)[0]
+        blocks.setdefault(key, []).append(name)
+    return list(blocks.values())
+
+
+def canonical_frozen(arena, frozen, heads="pretrain"):
+    """The pruning decision behind a pattern of frozen parameters: the names of the blocks that are frozen as a whole.  Two patterns with
+    the same result build the same plan, so this, not the pattern, is what a plan is keyed by; with only `query` frozen it is empty."""
+    frozen = set(frozen)
+    if not frozen:
+        return frozenset()
+    return frozenset(n for blk in frozen_blocks(arena, heads) if all(x in frozen for x in blk) for n in blk)
 
 
 class Stream:
@@ -66,7 +100,7 @@ class StepEngine(EmbeddingBuilders, SublayerBuilders, HeadBuilders):
     H8_MUL = 8.0           # static scale of the fp8 copy of the GELU output: |h| <= 56 representable, 2^-9 absolute resolution near 0
 
     def __init__(self, cfg, arena, B, T, Rv, train, heads="pretrain", fp8=False, task=None, task_dropout=0.1, attn_maps=False, part=None, split=None,
-                 projection_dtype=None):
+                 projection_dtype=None, frozen=None):
         """fp8: the forward Q|K|V, FFN-up and FFN-down projections of every sub-layer run on the e4m3 MFMA path (csrc/fp8.hip); inputs are
         quantised per row right before the GEMM, weights per output channel whenever they change; the backward stays bf16.
         heads: "pretrain" = the three pre-training heads and losses (BertForVLPreTraining); "tasks" = poolers only, the
@@ -78,11 +112,19 @@ class StepEngine(EmbeddingBuilders, SublayerBuilders, HeadBuilders):
         VL-logit classifier, or cls.bi_seq_relationship when task is None); `split` = retrieval.split_plan(cfg).
         projection_dtype: score plans only, None | "bf16" | "fp8" -- the scorer's own precision switch (the `fp8` argument belongs to the
         training plans and stays refused here).  "fp8" builds the same e4m3 launches as `fp8` does for a whole-model plan; a prefix plan then
-        exposes the e4m3 copy its last LayerNorm wrote as `score_x8`, and the pair plan starts from gathered copies (`pair_segments`)."""
+        exposes the e4m3 copy its last LayerNorm wrote as `score_x8`, and the pair plan starts from gathered copies (`pair_segments`).
+        frozen: arena names of parameters that take no gradient (requires_grad False).  The backward list keeps an op only if its output
+        reaches the gradient of a trainable parameter ("Frozen parameters"); the forward list, the buffers and, with
+        nothing frozen, both lists are what they are without the argument.  A block is pruned as a whole or not at all (`frozen_blocks`),
+        so any pattern may be passed: `canonical_frozen` maps it to the one the plan depends on.  Score plans have no backward and ignore it."""
         self.cfg, self.arena, self.B, self.T, self.Rv, self.train = cfg, arena, B, T, Rv, train
         self.heads = heads
         self.part, self.split = part, split
         self.fwd_only = heads == "score"   # the builders return before their backward part
+        self.frozen = frozenset() if self.fwd_only else canonical_frozen(arena, frozen or (), heads)
+        self.pruned = set()                # arena names whose gradient no op of the backward list writes: they read zero (modeling clears them once)
+        self.live = [True, True]           # builder state: a trainable parameter lies upstream of the current x[m], so its dX is needed
+        self.wgrad_recorded = set()        # sub-layers (index k) whose weight-gradient side block exists, i.e. whose ring event is recorded
         self.only = None                   # score prefixes: the one stream (0 text, 1 vision) whose problems a sub-layer emits
         if self.fwd_only and (train or fp8 or attn_maps or part not in ("text", "image", "pair") or split is None):
             raise ValueError("a score plan is an eval-mode forward of part text | image | pair with a split plan; its precision is projection_dtype, not fp8")
@@ -169,6 +211,23 @@ class StepEngine(EmbeddingBuilders, SublayerBuilders, HeadBuilders):
     def W(self, name):
         return self.arena.view(name, "shadow")
 
+    # ---- frozen parameters: `fz` asks; `prune` asks and notes that the caller leaves the block's gradient ops out
+    def fz(self, *names):
+        return bool(self.frozen) and all(n in self.frozen for n in names)
+
+    def prune(self, *names):
+        if self.fz(*names):
+            self.pruned.update(names)
+            return True
+        return False
+
+    def fz_linear(self, stem, prune=False):
+        """stem = "... .dense.": the weight and bias of one Linear, one block."""
+        return (self.prune if prune else self.fz)(stem + "weight", stem + "bias")
+
+    def prefix_names(self, prefix):
+        return [n for n in self.arena.params if n.startswith(prefix)]
+
     def Pm(self, name):
         return self.arena.view(name, "master")
 
@@ -179,6 +238,17 @@ class StepEngine(EmbeddingBuilders, SublayerBuilders, HeadBuilders):
         """geometry: tile code of vk_gemm_grouped_ex carried in the op's i0 above the layout (0 = the library's heuristic)"""
         arr = self.k((L.GemmProblem * len(probs))(*probs))
         self.put(plan_ops, L.OP_GEMM, arr, i0=layout | (geometry << 8), i1=epi, i2=len(probs))
+
+    def gemm_kept(self, plan_ops, layout, epi, probs, keep):
+        """`probs` in one launch, without those whose `keep` flag is False (frozen parameters: nothing reads their output).  The launch
+        keeps the tile geometry the library picks for the whole group, so what the remaining problems compute does not depend, to the bit, on
+        what else is frozen.  All kept: the launch of `gemm`."""
+        kept = [q for q, k in zip(probs, keep) if k]
+        if len(kept) == len(probs):
+            return self.gemm(plan_ops, layout, epi, probs)
+        if kept:
+            arr = (L.GemmProblem * len(probs))(*probs)
+            self.gemm(plan_ops, layout, epi, kept, geometry=L.lib.vk_gemm_geometry(layout, epi, arr, len(probs)))
 
     def prob(self, A, B, Cout, M, N, K, lda, ldb, ldc, bias=None, R=None, ldr=0, C2=None, bias_grad=None, dyn=None, n_store=0):
         return L.GemmProblem(_addr(A), _addr(B), _addr(Cout), _addr(C2), _addr(bias), _addr(R), _addr(bias_grad), _addr(dyn),
@@ -315,6 +385,9 @@ class StepEngine(EmbeddingBuilders, SublayerBuilders, HeadBuilders):
         block, next to main-stream LayerNorm backwards -- it cannot share their scratch records either."""
         H = H or self.H
         Hmax = max(self.st[0].H, self.st[1].H)
+        if self.prune(gname, bname):      # frozen gamma and beta: the launch without column sums -- no records, nothing to reduce later
+            return self.k(L.LnBwdArgs(_addr(dy), _addr(z), _addr(mean), _addr(rstd), _addr(self.Pm(gname)), _addr(dz), _addr(dd), None, None, None,
+                                      _addr(dyn), M, H, M, post, out_scale, 0, drop, _mk_segs(drop, segs)))
         if defer or own_partial or self._aside:
             self._n_ln_partial += 1
             partial = self.buf("ln_partial_%d" % self._n_ln_partial, (L.lib.vk_ln_bwd_partial_rows(M) * 2 * H,), torch.float32)
@@ -372,7 +445,7 @@ class StepEngine(EmbeddingBuilders, SublayerBuilders, HeadBuilders):
             if emb_image_aside:
                 f.insert(i0, side_begin())
                 f.append(side_end(EV_IMAGE_EMB_FWD))
-                emb_image_bwd = [side_begin()] + img_bwd + [side_end(EV_IMAGE_EMB_BWD)]
+                emb_image_bwd = [side_begin()] + img_bwd + [side_end(EV_IMAGE_EMB_BWD)] if img_bwd else []      # a frozen embedding: no block
                 bwd_stages.append([])
             else:
                 bwd_stages.append(img_bwd)
@@ -391,14 +464,15 @@ class StepEngine(EmbeddingBuilders, SublayerBuilders, HeadBuilders):
         self.sublayer_ids = [n for n, _ in sched]       # taps "t<n>" / "v<n>": both streams' states after sub-layer n, forward order
         backbone = self.heads == "backbone"
         v_level0 = []                 # backbone, vision embedding aside: seeds of vision states no sub-layer has transformed yet
+        sub_ops, n_head, sub_tail = [], [], []      # per sub-layer: its backward ops, how many seed ops lead them, what follows them in its stage
         for k, (n, typ) in enumerate(sched):
             self.sub_k = k
             self.fwd_sub_start.append(len(self.fwd.ops))
             if emb_image_aside and k == k_vis:
                 f.append(wait_side(EV_IMAGE_EMB_FWD))       # the vision stream enters here: its embedding must be complete
             ops = self._attn_sublayer(n) if typ == "attn" else self._ffn_sublayer(n)
-            if k + 2 < self.n_sub:
-                ops.insert(0, wait_side((k + 2) % EV_WGRAD_RING))
+            sub_ops.append(ops)
+            n_head.append(0)
             if backbone and k + 1 < self.n_sub:
                 # d(loss)/d(state after sub-layer n), output_all_encoded_layers: added into the stream's current dX buffer at the head of the
                 # sub-layer's backward stage, before anything reads it (the final states are the seeds of the heads' backward).  A stream the
@@ -407,18 +481,37 @@ class StepEngine(EmbeddingBuilders, SublayerBuilders, HeadBuilders):
                 # the untransformed vision states go in front of that fork instead
                 head = []
                 for m, tag in ((0, "t"), (1, "v")):
+                    if not self.live[m]:          # no trainable parameter upstream of this state: its gradient is carried no further
+                        continue
                     self._seed_op(v_level0 if (m == 1 and emb_image_aside and self.level[1] == 0) else head,
                                   "%s%d" % (tag, n), self._dx(m, self.level[m] % 2), self.B, self.st[m].L, self.st[m].H, accumulate=1)
                 ops[0:0] = head
-            if emb_image_aside and k == k_vis:
-                ops = ops + v_level0 + emb_image_bwd                        # d(loss)/d(vision embedding) is final after this sub-layer's backward
-            bwd_stages.append(ops)
+                n_head[k] = len(head)
+            sub_tail.append((v_level0 + emb_image_bwd) if (emb_image_aside and k == k_vis) else [])      # d(loss)/d(vision embedding) is final after this sub-layer's backward
             self.taps["t%d" % n], self.taps["v%d" % n] = self.x[0], self.x[1]
+        # sub-layer k's backward first waits for the weight-gradient block of sub-layer k + 2, the previous user of its set of temporaries
+        # (plan.py) -- where that block exists: a sub-layer whose blocks are all frozen has none and records no event
+        for k, ops in enumerate(sub_ops):
+            if k + 2 < self.n_sub and (k + 2) in self.wgrad_recorded:
+                ops.insert(n_head[k], wait_side((k + 2) % EV_WGRAD_RING))
+            bwd_stages.append(ops + sub_tail[k])
         self.fwd_heads_start = len(self.fwd.ops)
         head_bwd = self._heads() if self.heads == "pretrain" else self._heads_tasks()
         # backward list: zero-fills, heads, then stages in reverse; bwd_marks[s] = op index at which backward
         # stage s is complete (stage 0 = heads), param_ready_stage[name] = stage after which its gradient is final
         self.bwd.ops = list(self.bwd_pro) + list(head_bwd)
+        if self.frozen:
+            # A wait whose event the pruned list no longer records goes with the block that recorded it.  EV_DECODER_WGRAD is recorded by the
+            # pre-training heads only: the text tables of the other plans wait for it in the unpruned list as well, and go on doing so.
+            recorded = set() if self.heads == "pretrain" else {EV_DECODER_WGRAD}
+            for ops in [self.bwd.ops] + bwd_stages[::-1]:
+                kept = []
+                for o in ops:
+                    if o[0] == L.OP_SIDE_END:
+                        recorded.add(o[1])
+                    if o[0] != L.OP_WAIT_SIDE or o[1] in recorded:
+                        kept.append(o)
+                ops[:] = kept
         self.bwd_marks = [len(self.bwd.ops)]
         for ops in reversed(bwd_stages):
             self.bwd.ops += ops

@@ -8,6 +8,15 @@ from .plan import EV_DECODER_WGRAD, NODROP, _addr, _round_up, wait_side
 class EmbeddingBuilders:
     """Base class of StepEngine.  Every builder appends its forward ops to `self.fwd.ops`, sets `self.x` and returns its backward ops."""
 
+    def _emb_frozen(self, pre, streams):
+        """Every parameter under the embedding prefix `pre` is frozen: the embedding takes no backward ("Frozen
+        parameters"), and no trainable parameter lies upstream of the `streams` it starts.  An embedding with a trainable parameter runs
+        its whole backward."""
+        off = self.prune(*self.prefix_names(pre))
+        for m in streams:
+            self.live[m] = not off
+        return off
+
     def embed_ws(self, eb, tag):
         """Workspace of one embedding backward (vk_embed_sum_bwd: the fixed-order partial sums of its table rows), set into its arguments."""
         n = L.lib.vk_embed_bwd_workspace_bytes(eb.M, eb.H, eb.V, eb.P, int(bool(eb.pos_ids) and bool(eb.dpos)))
@@ -43,7 +52,7 @@ class EmbeddingBuilders:
         dr = self.drop(cfg.hidden_dropout_prob)
         self.ln_fwd(self.fwd.ops, z, None, pre + "LayerNorm.weight", pre + "LayerNorm.bias", y, None, mean, rstd, st.M, dr, post=1)
         self.x[0] = y
-        if self.fwd_only:
+        if self.fwd_only or self._emb_frozen(pre, (0,)):
             return []
         b = []
         dz = self.tmp("dz0", (st.M, H))
@@ -102,7 +111,7 @@ class EmbeddingBuilders:
         dr = self.drop(cfg.v_hidden_dropout_prob)
         self.ln_fwd(self.fwd.ops, proj, loc, pre + "LayerNorm.weight", pre + "LayerNorm.bias", y, proj, mean, rstd, st.M, dr, post=1, H=H)
         self.x[1] = y
-        if self.fwd_only:
+        if self.fwd_only or self._emb_frozen(pre, (1,)):
             return []
         b = []
         dz = self.tmp("dz1", (st.M, H))
@@ -141,7 +150,7 @@ class EmbeddingBuilders:
         dr = self.drop(cfg.v_hidden_dropout_prob)
         self.emit(self.fwd.ops, L.FN_ADD_DROPOUT, p=(a_n, b_n, y), n=(st.M, H, 0), f=(0.5,), drop=dr)
         self.x[1] = y
-        if self.fwd_only:
+        if self.fwd_only or self._emb_frozen(pre, (1,)):
             return []
         b = []
         g = self.tmp("dz1", (st.M, H))
@@ -158,7 +167,7 @@ class EmbeddingBuilders:
         type1 = self.Pm(pre + "token_type_embeddings.weight")[1]
         self.ln_fwd(self.fwd.ops, a_n, b_n, pre + "v_LayerNorm.weight", pre + "v_LayerNorm.bias", y, z, mean, rstd, st.M, dr, post=1, addvec=type1)
         self.x[1] = y
-        if self.fwd_only:
+        if self.fwd_only or self._emb_frozen(pre, (1,)):          # one prefix with the text tables: frozen together or not at all
             return []
         b = []
         dz = self.tmp("dz1", (st.M, H))
@@ -213,7 +222,7 @@ class EmbeddingBuilders:
         zv = self.buf("emb_v_z", (st_v.M, H))
         stats = [self.buf("emb_%s" % s, (m,), torch.float32) for s, m in (("t_mean", st_t.M), ("t_rstd", st_t.M), ("v_mean", st_v.M), ("v_rstd", st_v.M))]
         ln = self._concat_ln_fwd(pre, zt, proj, stats, zv=zv, addvec=vec)
-        if self.fwd_only:
+        if self.fwd_only or self._emb_frozen(pre, (0, 1)):
             return []
         b = []
         dzt, dzv = self._concat_ln_bwd(b, ln, zt, zv)
@@ -290,7 +299,7 @@ class EmbeddingBuilders:
         tz = self.buf("emb_t_z", (st_t.M, H))
         self._text_tables_fwd(pre, tz, pos_ids=tpos, add=tvx)
         ln = self._concat_ln_fwd(pre, tz, vz, so[4:])
-        if self.fwd_only:
+        if self.fwd_only or self._emb_frozen(pre, (0, 1)):
             return []
         # ---- backward
         b = []

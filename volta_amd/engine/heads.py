@@ -24,10 +24,17 @@ class HeadBuilders:
         return pt, pv
 
     def _pooler_bwd(self, b, wg, m, dy, dxh):
-        """Stream m's pooler from dy [B, P] back: added into rows b * L of dxh[m] (every sample's first token); weight gradient listed in `wg`."""
+        """Stream m's pooler from dy [B, P] back: added into rows b * L of dxh[m] (every sample's first token); weight gradient listed in `wg`.
+        Frozen parameters: the dgrad only where the stream's dX is needed, the weight gradient only for a trainable pooler."""
         B, P, Lm, Hm, pre = self.B, self.cfg.pooler_size, self.st[m].L, self.st[m].H, ("bert.t_pooler.dense.", "bert.v_pooler.dense.")[m]
-        self.gemm(b, L.NN, L.EPI_ADDR, [self.prob(dy, self.W(pre + "weight"), dxh[m], B, Hm, P, P, Hm, Lm * Hm, R=dxh[m], ldr=Lm * Hm)])
-        self.gemm(wg, L.TN, L.EPI_F32, [self.prob(dy, self.x[m], self.G(pre + "weight"), P, Hm, B, P, Lm * Hm, Hm, bias_grad=self.G(pre + "bias"))])
+        if self.live[m]:
+            self.gemm(b, L.NN, L.EPI_ADDR, [self.prob(dy, self.W(pre + "weight"), dxh[m], B, Hm, P, P, Hm, Lm * Hm, R=dxh[m], ldr=Lm * Hm)])
+        if not self.fz_linear(pre, prune=True):
+            self.gemm(wg, L.TN, L.EPI_F32, [self.prob(dy, self.x[m], self.G(pre + "weight"), P, Hm, B, P, Lm * Hm, Hm, bias_grad=self.G(pre + "bias"))])
+
+    def _pool_grad_needed(self, m):
+        """Does anything read the gradient at stream m's pooled vector: its pooler's weights, or the stream below it?"""
+        return self.live[m] or not self.fz_linear(("bert.t_pooler.dense.", "bert.v_pooler.dense.")[m])
 
     def _transform_fwd(self, tag, c, x, rows, count, M, Hm, ln=True):
         """cls.*.transform on the labelled rows of x: gather -> dense + GELU -> LayerNorm (where `ln`).  -> (transformed rows, state for _transform_bwd)."""
@@ -44,16 +51,28 @@ class HeadBuilders:
     def _transform_bwd(self, b, wg, tmp, state, dhn, dx, own_partial=False):
         """From dhn (temporary `tmp`_d1) back into the labelled rows of dx (scatter-add); the dense layer's weight gradient is listed in `wg`."""
         w, hx, h, gp, mean, rstd, rows, count, M, Hm = state
+        # frozen parameters: `dx` None = the stream's dX is not needed; every step below runs only if something trainable reads its output
+        dense_on = not self.fz_linear(w + "dense.", prune=True)
+        need_du = dx is not None or dense_on
         dh = dhn
         if mean is not None:
             dh = self.tmp(tmp + "_d2", (M, Hm))
-            self.ln_bwd(b, dhn, h, mean, rstd, w + "LayerNorm.weight", w + "LayerNorm.bias", dh, None, M, NODROP, dyn=count, own_partial=own_partial, H=Hm)
+            if need_du or not self.fz(w + "LayerNorm.weight", w + "LayerNorm.bias"):
+                self.ln_bwd(b, dhn, h, mean, rstd, w + "LayerNorm.weight", w + "LayerNorm.bias", dh if need_du else None, None, M, NODROP, dyn=count,
+                            own_partial=own_partial, H=Hm)
+            else:
+                self.prune(w + "LayerNorm.weight", w + "LayerNorm.bias")
+        if not need_du:
+            return
         du = self.tmp(tmp + "_d3", (M, Hm))
         self.emit(b, L.FN_MUL, p=(dh, gp, du, count), n=(M * Hm, Hm))
         dhx = self.tmp(tmp + ("_d2" if mean is None else "_d1"), (M, Hm))
-        self.gemm(b, L.NN, L.EPI_BF16, [self.prob(du, self.W(w + "dense.weight"), dhx, M, Hm, Hm, Hm, Hm, Hm, dyn=count)])
-        self.gemm(wg, L.TN, L.EPI_F32, [self.prob(du, hx, self.G(w + "dense.weight"), Hm, Hm, M, Hm, Hm, Hm, bias_grad=self.G(w + "dense.bias"), dyn=count)])
-        self.emit(b, L.FN_SCATTER_ADD, p=(dhx, rows, count, dx), n=(Hm, M))
+        if dx is not None:
+            self.gemm(b, L.NN, L.EPI_BF16, [self.prob(du, self.W(w + "dense.weight"), dhx, M, Hm, Hm, Hm, Hm, Hm, dyn=count)])
+        if dense_on:
+            self.gemm(wg, L.TN, L.EPI_F32, [self.prob(du, hx, self.G(w + "dense.weight"), Hm, Hm, M, Hm, Hm, Hm, bias_grad=self.G(w + "dense.bias"), dyn=count)])
+        if dx is not None:
+            self.emit(b, L.FN_SCATTER_ADD, p=(dhx, rows, count, dx), n=(Hm, M))
 
     def _heads(self):
         cfg, B, H, T, Rv, R = self.cfg, self.B, self.H, self.T, self.Rv, self.R
@@ -163,35 +182,58 @@ class HeadBuilders:
         # ================= backward of the heads: produces dX[0], dX[1].  Three independent chains of small launches, each with temporaries of
         # its own: the masked-LM and ITM chains stay on the caller's stream, the region chain (with its weight gradients) runs on the side
         # stream next to them, and every weight gradient of the two main chains follows in a second side block (events: plan.py).
+        # Frozen parameters: a chain runs as far down as something trainable reads it -- its own parameters, or the
+        # stream below the heads (`self.live`); a weight gradient only for a trainable block.
         b, wg = [], []
         dxh = [self._dx(m, self.level[m] % 2) for m in range(2)]
+        live = list(self.live)
         for m in range(2):
-            self.zero(b, dxh[m])
+            if live[m]:
+                self.zero(b, dxh[m])
+        tr_on = lambda c: not self.fz(*self.prefix_names(c + "transform."))
         # ---- region chain (side stream)
-        b.append(side_begin())
+        dec_on = [not self.fz_linear(ci + "decoder_dict.%s." % ix, prune=True) for ix, _, _, _, _ in vis]
+        need_dhn_v = live[1] or tr_on(ci)
+        rb = []
         dhn_v = self.tmp("head_v_d1", (Mr, Hv))
         for j, (ix, Cn, Cp, la, tag) in enumerate(vis):
             dlog_v = self.buf(tag + "_dlogits", (Mr, Cp))
+            if not (need_dhn_v or dec_on[j]):
+                continue
             if ix == "0":
-                self.put(b, L.OP_KL_BWD, la, dlog_v, self.gout[1:2], i0=Cp)
+                self.put(rb, L.OP_KL_BWD, la, dlog_v, self.gout[1:2], i0=Cp)
             else:
-                self.emit(b, L.FN_VIS_LOSS_BWD, p=(la, dlog_v, self.gout[1:2]), n=(Cp,))
+                self.emit(rb, L.FN_VIS_LOSS_BWD, p=(la, dlog_v, self.gout[1:2]), n=(Cp,))
             wdec = ci + "decoder_dict.%s." % ix
-            if j == 0:
-                self.gemm(b, L.NN, L.EPI_BF16, [self.prob(dlog_v, self.W(wdec + "weight"), dhn_v, Mr, Hv, Cn, Cp, Hv, Hv, dyn=n_v)])
+            if not need_dhn_v:
+                pass
+            elif j == 0:
+                self.gemm(rb, L.NN, L.EPI_BF16, [self.prob(dlog_v, self.W(wdec + "weight"), dhn_v, Mr, Hv, Cn, Cp, Hv, Hv, dyn=n_v)])
             else:                                               # the decoders share the transformed hidden state: their input gradients add up
-                self.gemm(b, L.NN, L.EPI_ADDR, [self.prob(dlog_v, self.W(wdec + "weight"), dhn_v, Mr, Hv, Cn, Cp, Hv, Hv, dyn=n_v, R=dhn_v, ldr=Hv)])
-            self.gemm(b, L.TN, L.EPI_F32, [self.prob(dlog_v, hn_v, self.G(wdec + "weight"), Cn, Hv, Mr, Cp, Hv, Hv, bias_grad=self.G(wdec + "bias"), dyn=n_v)])
-        self._transform_bwd(b, b, "head_v", img_tr, dhn_v, dxh[1], own_partial=True)
-        b.append(side_end(EV_HEAD_REGIONS_BWD))
+                self.gemm(rb, L.NN, L.EPI_ADDR, [self.prob(dlog_v, self.W(wdec + "weight"), dhn_v, Mr, Hv, Cn, Cp, Hv, Hv, dyn=n_v, R=dhn_v, ldr=Hv)])
+            if dec_on[j]:
+                self.gemm(rb, L.TN, L.EPI_F32, [self.prob(dlog_v, hn_v, self.G(wdec + "weight"), Cn, Hv, Mr, Cp, Hv, Hv, bias_grad=self.G(wdec + "bias"), dyn=n_v)])
+        if need_dhn_v:
+            self._transform_bwd(rb, rb, "head_v", img_tr, dhn_v, dxh[1] if live[1] else None, own_partial=True)
+        else:
+            self.prune(*self.prefix_names(ci + "transform."))
+        if rb:
+            b += [side_begin()] + rb + [side_end(EV_HEAD_REGIONS_BWD)]
         # ---- masked-LM chain
+        dec_t_on = not self.prune(wword, c + "bias")
+        if dec_t_on:
+            self.pruned.discard(wword)           # frozen with its embedding, but still written here with the trainable decoder bias
+        need_dhn_t = live[0] or tr_on(c)
         dlog_t = self.buf("lm_dlogits", (st_t.M, Vp))
-        self.put(b, L.OP_XENT_BWD, xa, dlog_t, self.gout[0:1], i0=Vp)
+        if need_dhn_t or dec_t_on:
+            self.put(b, L.OP_XENT_BWD, xa, dlog_t, self.gout[0:1], i0=Vp)
         dhn_t = self.tmp("head_d1", (st_t.M, H))
         # d(hidden) = dlogits[n_t, V] . E[V, H]: few rows, very long contraction -> split K over the vocabulary into
         # chunks written as fp32 slabs by one grouped launch, then summed (and rounded to bf16) in one pass
         nsplit = max(1, min(16, V // 1920))
-        if nsplit == 1:
+        if not need_dhn_t:
+            pass
+        elif nsplit == 1:
             self.gemm(b, L.NN, L.EPI_BF16, [self.prob(dlog_t, self.W(wword), dhn_t, st_t.M, H, V, Vp, H, H, dyn=n_t)])
         else:
             kc = _round_up(-(-V // nsplit), 64)
@@ -205,26 +247,43 @@ class HeadBuilders:
                 k0 += kc
             self.gemm(b, L.NN, L.EPI_F32, probs)
             self.emit(b, L.FN_SUM_SLABS_BF16, p=(dhn_t, slabs, n_t), n=(stride, len(probs), stride, H))
-        self.gemm(wg, L.TN, L.EPI_F32, [self.prob(dlog_t, hn_t, self.G(wword), V, H, st_t.M, Vp, H, H, bias_grad=self.G(c + "bias"), dyn=n_t)])
-        self._transform_bwd(b, wg, "head", lm_tr, dhn_t, dxh[0])
+        if dec_t_on:
+            self.gemm(wg, L.TN, L.EPI_F32, [self.prob(dlog_t, hn_t, self.G(wword), V, H, st_t.M, Vp, H, H, bias_grad=self.G(c + "bias"), dyn=n_t)])
+        elif not self.fz(*self.prefix_names("bert.embeddings.")):
+            # the text tables' backward adds to the word table's gradient, which the decoder's weight gradient no longer initialises
+            self.zero(self.bwd_pro, self.G(wword))
+            self.pruned.discard(wword)
+        if need_dhn_t:
+            self._transform_bwd(b, wg, "head", lm_tr, dhn_t, dxh[0] if live[0] else None)
+        else:
+            self.prune(*self.prefix_names(c + "transform."))
         # ---- ITM chain
         if has_itm:
-            dlog_i = self.buf("itm_dlogits", (B, 64))
-            self.put(b, L.OP_XENT_BWD, xi, dlog_i, self.gout[2:3], i0=64)
-            dpooled = self.buf("d_pooled", (B, P))
             wi = "cls.bi_seq_relationship."
-            self.gemm(b, L.NN, L.EPI_BF16, [self.prob(dlog_i, self.W(wi + "weight"), dpooled, B, P, 2, 64, P, P)])
-            self.gemm(wg, L.TN, L.EPI_F32, [self.prob(dlog_i, pooled, self.G(wi + "weight"), 2, P, B, 64, P, P, bias_grad=self.G(wi + "bias"))])
+            itm_on = not self.fz_linear(wi, prune=True)
+            need_pool = [self._pool_grad_needed(0), pv is not None and self._pool_grad_needed(1)]
+            dlog_i = self.buf("itm_dlogits", (B, 64))
+            if itm_on or any(need_pool):
+                self.put(b, L.OP_XENT_BWD, xi, dlog_i, self.gout[2:3], i0=64)
+            dpooled = self.buf("d_pooled", (B, P))
+            if any(need_pool):
+                self.gemm(b, L.NN, L.EPI_BF16, [self.prob(dlog_i, self.W(wi + "weight"), dpooled, B, P, 2, 64, P, P)])
+            if itm_on:
+                self.gemm(wg, L.TN, L.EPI_F32, [self.prob(dlog_i, pooled, self.G(wi + "weight"), 2, P, B, 64, P, P, bias_grad=self.G(wi + "bias"))])
             dyt = self.buf("d_pool_t", (B, P))
             dyv = self.buf("d_pool_v", (B, P)) if pv is not None else None
-            self.emit(b, L.FN_POOL_BWD, p=(dpooled, pt, pv, dyt, dyv), n=(B, P, P, fuse), drop=pdrop)
+            if any(need_pool):
+                self.emit(b, L.FN_POOL_BWD, p=(dpooled, pt, pv, dyt, dyv), n=(B, P, P, fuse), drop=pdrop)
             for m, dy_ in ((0, dyt), (1, dyv)):          # rows b * L: disjoint from the labelled rows the region chain scatters into
-                if dy_ is not None:
+                if dy_ is not None and need_pool[m]:
                     self._pooler_bwd(b, wg, m, dy_, dxh)
+                elif dy_ is not None:
+                    self.fz_linear(("bert.t_pooler.dense.", "bert.v_pooler.dense.")[m], prune=True)
         # ---- the main chains' weight gradients, off the critical path
-        b.append(side_begin())
-        b += wg
-        b.append(side_end(EV_DECODER_WGRAD))
+        if wg:
+            b.append(side_begin())
+            b += wg
+            b.append(side_end(EV_DECODER_WGRAD))
         b.append(wait_side(EV_HEAD_REGIONS_BWD))            # dX[1] is complete
         return b
 
@@ -268,12 +327,17 @@ class HeadBuilders:
         # The word-embedding gradient is accumulated with atomics by the embedding backward; in the pre-training model the LM
         # decoder's weight gradient (same tied tensor) is what initialises it, here nothing else writes it: zero it per step.
         for nm in self.arena.params:
-            if nm.endswith("embeddings.word_embeddings.weight"):
+            if nm.endswith("embeddings.word_embeddings.weight") and not self.fz(*self.prefix_names(nm[:-len("word_embeddings.weight")])):
                 self.zero(self.bwd_pro, self.G(nm))
+        # Frozen parameters: a step of the backward runs only if something trainable reads its output -- the
+        # parameters of the step before it, or the stream below the heads (`self.live`); a weight gradient only for a trainable block.
         b = []
         dxh = [self._dx(m, self.level[m] % 2) for m in range(2)]
+        live = list(self.live)
         backbone = self.heads == "backbone"
         for m in range(2):
+            if not live[m]:
+                continue
             if backbone:                                   # d(loss)/d(seq_t), d(loss)/d(seq_v) from outside, written before the poolers add theirs
                 self._seed_op(b, ("seq_t", "seq_v")[m], dxh[m], B, self.st[m].L, self.st[m].H)
             else:                                          # the sequence outputs feed nothing but the task head
@@ -287,7 +351,8 @@ class HeadBuilders:
             for m, (py, nm) in enumerate(((pt, "pooled_t"), (pv, "pooled_v"))):
                 if py is not None:                         # ReLU poolers: d pre-activation = d pooled * (pooled > 0)
                     dpool[m] = self.buf("d_" + nm, (B, P))
-                    self._seed_op(b, nm, dpool[m], B, 1, P, y=py)
+                    if self._pool_grad_needed(m):
+                        self._seed_op(b, nm, dpool[m], B, 1, P, y=py)
         elif self.task is not None:
             task_id, tcfg = self.task
             typ = tcfg["type"]
@@ -301,9 +366,11 @@ class HeadBuilders:
                 self.gemm(f, L.NT, L.EPI_F32, [self.prob(x, self.W(wname + "weight"), out, rows, C, K, K, K, Cp, bias=self.Pm(wname + "bias"), n_store=Cp)])
                 return out, self.buf("task_dlogits", (rows, Cp), zero=True), Cp
 
-            def linear_bwd(dlog, Cp, x, rows, K, wname, C, dx):
-                self.gemm(b, L.NN, L.EPI_BF16, [self.prob(dlog, self.W(wname + "weight"), dx, rows, K, C, Cp, K, K)])
-                self.gemm(b, L.TN, L.EPI_F32, [self.prob(dlog, x, self.G(wname + "weight"), C, K, rows, Cp, K, K, bias_grad=self.G(wname + "bias"))])
+            def linear_bwd(dlog, Cp, x, rows, K, wname, C, dx, need_dx=True):
+                if need_dx:
+                    self.gemm(b, L.NN, L.EPI_BF16, [self.prob(dlog, self.W(wname + "weight"), dx, rows, K, C, Cp, K, K)])
+                if not self.fz_linear(wname, prune=True):
+                    self.gemm(b, L.TN, L.EPI_F32, [self.prob(dlog, x, self.G(wname + "weight"), C, K, rows, Cp, K, K, bias_grad=self.G(wname + "bias"))])
 
             if typ.startswith("V-logit"):
                 Mv = st_v.M
@@ -318,16 +385,22 @@ class HeadBuilders:
                     self.emit(f, L.FN_ADD_DROPOUT, p=(h, None, hd), n=(Mv, Hv, 0), f=(1.0,), drop=d1)
                     self.pred, self.d_pred, Cp = linear_out(hd, Mv, Hv, pre + "3.", 1)
                     dhd, dh, du = self.buf("task_dhd", (Mv, Hv)), self.buf("task_dh", (Mv, Hv)), self.buf("task_du", (Mv, Hv))
-                    linear_bwd(self.d_pred, Cp, hd, Mv, Hv, pre + "3.", 1, dhd)
-                    self.emit(b, L.FN_ADD_DROPOUT, p=(dhd, None, dh), n=(Mv, Hv, 1), f=(1.0,), drop=d1)
-                    self.emit(b, L.FN_MUL, p=(dh, gp, du, None), n=(Mv * Hv, Hv))
+                    need_du = live[1] or not self.fz_linear(pre + "0.")
+                    linear_bwd(self.d_pred, Cp, hd, Mv, Hv, pre + "3.", 1, dhd, need_du)
+                    if need_du:
+                        self.emit(b, L.FN_ADD_DROPOUT, p=(dhd, None, dh), n=(Mv, Hv, 1), f=(1.0,), drop=d1)
+                        self.emit(b, L.FN_MUL, p=(dh, gp, du, None), n=(Mv * Hv, Hv))
                     dxd = self.buf("task_dxd", (Mv, Hv))
-                    linear_bwd(du, Hv, xd, Mv, Hv, pre + "0.", Hv, dxd)
+                    if need_du:
+                        linear_bwd(du, Hv, xd, Mv, Hv, pre + "0.", Hv, dxd, live[1])
+                    else:
+                        self.fz_linear(pre + "0.", prune=True)
                 else:
                     self.pred, self.d_pred, Cp = linear_out(xd, Mv, Hv, pre, 1)
                     dxd = self.buf("task_dxd", (Mv, Hv))
-                    linear_bwd(self.d_pred, Cp, xd, Mv, Hv, pre, 1, dxd)
-                self.emit(b, L.FN_ADD_DROPOUT, p=(dxd, None, dxh[1]), n=(Mv, Hv, 1), f=(1.0,), drop=d0)
+                    linear_bwd(self.d_pred, Cp, xd, Mv, Hv, pre, 1, dxd, live[1])
+                if live[1]:
+                    self.emit(b, L.FN_ADD_DROPOUT, p=(dxd, None, dxh[1]), n=(Mv, Hv, 1), f=(1.0,), drop=d0)
                 self.pred_shape = (B, Rv, 1)
             else:
                 if fm == "none":
@@ -340,6 +413,7 @@ class HeadBuilders:
                 if typ == "VL-binary-classifier" and B % 2:
                     raise ValueError("VL-binary-classifier pools pairs of samples: the batch size must be even")
                 dpooled = self.buf("d_pooled", (B, P))
+                need_p = self._pool_grad_needed(0) or (pv is not None and self._pool_grad_needed(1))
                 if typ in ("VL-classifier", "VL-classifier-GQA", "VL-binary-classifier"):
                     C = 2 if typ == "VL-binary-classifier" else int(tcfg["num_labels"])
                     Hc = cfg.clf_hidden_size
@@ -353,21 +427,29 @@ class HeadBuilders:
                     self.ln_fwd(f, hc, None, lnn + "weight", lnn + "bias", hn, None, mean, rstd, rows, NODROP, H=Hc)
                     self.pred, self.d_pred, Cp = linear_out(hn, rows, Hc, w3, C)
                     dhn, dhc, du = self.buf("task_dhn", (rows, Hc)), self.buf("task_dhc", (rows, Hc)), self.buf("task_du", (rows, Hc))
-                    linear_bwd(self.d_pred, Cp, hn, rows, Hc, w3, C, dhn)
+                    need_du = need_p or not self.fz_linear(w0)
+                    ln_off = self.prune(lnn + "weight", lnn + "bias")
+                    linear_bwd(self.d_pred, Cp, hn, rows, Hc, w3, C, dhn, need_du or not ln_off)
                     part = self.buf("task_ln_partial", (L.lib.vk_ln_bwd_partial_rows(rows) * 2 * Hc,), torch.float32)
-                    lb = L.LnBwdArgs(_addr(dhn), _addr(hc), _addr(mean), _addr(rstd), _addr(self.Pm(lnn + "weight")), _addr(dhc), None, _addr(part),
-                                     _addr(self.G(lnn + "weight")), _addr(self.G(lnn + "bias")), None, rows, Hc, rows, 0, 1.0, 0, NODROP, _mk_segs(NODROP, None))
-                    self.put(b, L.OP_LN_BWD, self.k(lb))
-                    self.emit(b, L.FN_MUL, p=(dhc, gpc, du, None), n=(rows * Hc, Hc))
-                    linear_bwd(du, Hc, pooled, rows, K0, w0, Hc, dpooled)
+                    if need_du or not ln_off:
+                        lb = L.LnBwdArgs(_addr(dhn), _addr(hc), _addr(mean), _addr(rstd), _addr(self.Pm(lnn + "weight")), _addr(dhc) if need_du else None, None,
+                                         None if ln_off else _addr(part), None if ln_off else _addr(self.G(lnn + "weight")),
+                                         None if ln_off else _addr(self.G(lnn + "bias")), None, rows, Hc, rows, 0, 1.0, 0, NODROP, _mk_segs(NODROP, None))
+                        self.put(b, L.OP_LN_BWD, self.k(lb))
+                    if need_du:
+                        self.emit(b, L.FN_MUL, p=(dhc, gpc, du, None), n=(rows * Hc, Hc))
+                        linear_bwd(du, Hc, pooled, rows, K0, w0, Hc, dpooled, need_p)
+                    else:
+                        self.fz_linear(w0, prune=True)
                 else:                                         # VL-tri-classifier (3 classes), VL-logit (1 score): one Linear (:1134-1137)
                     C = 3 if typ == "VL-tri-classifier" else 1
                     self.pred, self.d_pred, Cp = linear_out(pooled, rows, K0, pre, C)
-                    linear_bwd(self.d_pred, Cp, pooled, rows, K0, pre, C, dpooled)
+                    linear_bwd(self.d_pred, Cp, pooled, rows, K0, pre, C, dpooled, need_p)
                 self.pred_shape = (rows, C)
                 dpool[0] = self.buf("d_pool_t", (B, P))
                 dpool[1] = self.buf("d_pool_v", (B, P)) if pv is not None else None
-                self.emit(b, L.FN_POOL_BWD, p=(dpooled, pt, pv, dpool[0], dpool[1]), n=(B, P, P, fuse), drop=d0)
+                if need_p:
+                    self.emit(b, L.FN_POOL_BWD, p=(dpooled, pt, pv, dpool[0], dpool[1]), n=(B, P, P, fuse), drop=d0)
         self.unused_params |= set(heads_of_other_tasks)      # the classifiers of the other tasks (and, for region-logit tasks, the poolers) get no gradient
         for m, (pre_p, py) in enumerate((("bert.t_pooler.dense.", pt), ("bert.v_pooler.dense.", pv))):
             if py is None:
@@ -375,11 +457,15 @@ class HeadBuilders:
             if dpool[m] is None:
                 self.unused_params |= {pre_p + "weight", pre_p + "bias"}
                 continue
-            if vqa is not None:                            # the pooled token differs per caption: gathered rows in, scatter-add out
+            if not self._pool_grad_needed(m):
+                self.fz_linear(pre_p, prune=True)
+            elif vqa is not None:                          # the pooled token differs per caption: gathered rows in, scatter-add out
                 dxg = self.buf("vqa_dx", (B, H))
-                self.gemm(b, L.NN, L.EPI_BF16, [self.prob(dpool[m], self.W(pre_p + "weight"), dxg, B, H, P, P, H, H)])
-                self.emit(b, L.FN_SCATTER_ADD, p=(dxg, vqa_rows, vqa_cnt, dxh[0]), n=(H, B))
-                self.gemm(b, L.TN, L.EPI_F32, [self.prob(dpool[m], xg, self.G(pre_p + "weight"), P, H, B, P, H, H, bias_grad=self.G(pre_p + "bias"))])
+                if live[0]:
+                    self.gemm(b, L.NN, L.EPI_BF16, [self.prob(dpool[m], self.W(pre_p + "weight"), dxg, B, H, P, P, H, H)])
+                    self.emit(b, L.FN_SCATTER_ADD, p=(dxg, vqa_rows, vqa_cnt, dxh[0]), n=(H, B))
+                if not self.fz_linear(pre_p, prune=True):
+                    self.gemm(b, L.TN, L.EPI_F32, [self.prob(dpool[m], xg, self.G(pre_p + "weight"), P, H, B, P, H, H, bias_grad=self.G(pre_p + "bias"))])
             else:
                 self._pooler_bwd(b, b, m, dpool[m], dxh)
         return b

@@ -112,30 +112,48 @@ class SublayerBuilders:
         if self.fwd_only:
             return []
         # ------------- backward
+        # Frozen parameters: the attention launch serves both streams, so the sub-layer's backward runs for all of its
+        # streams or for none -- none when no stream has a trainable parameter in the sub-layer or upstream of its input.  Per stream, the
+        # input gradient (the last dgrad and the LayerNorm's dz) is computed only where a trainable parameter lies upstream of that input.
+        live_in = list(self.live)
+        qkv_all = lambda m: qkv_names(m, ".weight") + qkv_names(m, ".bias")
+        ln_of = lambda m: (names[m]["ln"] + ".weight", names[m]["ln"] + ".bias")
+        o_of = lambda m: (names[m]["o"] + ".weight", names[m]["o"] + ".bias")
+        if not any(live_in[m] or not self.fz(*qkv_all(m), *o_of(m), *ln_of(m)) for m in ms):
+            for m in ms:
+                self._dx_step(m)               # the ping-pong parity of dX counts every sub-layer
+                self.prune(*qkv_all(m), *o_of(m), *ln_of(m))
+            return []
+        for m in ms:
+            self.live[m] = True
         b = []
-        dz, dd, dxn = self._tail_bwd(b, tail, shared)
+        need_dqkv = any(live_in[m] or not self.fz(*qkv_all(m)) for m in ms)      # else nothing reads past dd: o's weight gradient and the LayerNorm's are all
+        dz, dd, dxn = self._tail_bwd(b, tail, shared, need_dz=live_in)
         dctx, dqkv, par = {}, {}, self.sub_k % 2
         for m in ms:
             wtag = "" if Ha[m] == Hm[m] == self.H else "_%d" % Ha[m]      # temporaries are shared by name: other widths get their own
             dctx[m] = self.tmp("dctx%d%s" % (m, wtag), (self.st[m].M, Ha[m]))
             dqkv[m] = self.tmp("dqkv%d_%d%s" % (m, par, wtag), (self.st[m].M, 3 * Ha[m]))
-        self.gemm(b, L.NN, L.EPI_BF16, [self.prob(dd[m], self.W(names[m]["o"] + ".weight"), dctx[m], self.st[m].M, Ha[m], Hm[m], Hm[m], Ha[m], Ha[m]) for m in ms])
-        for m in ms:
-            if not (gate[0][m] or gate[1][m]):       # K/V of this modality unused: their gradient is zero
-                self.zero(b, dqkv[m])
-        for aa, mq, gl in attn:
-            ab = L.AttnBwdArgs()
-            for m in mq:
-                ab.dctx[m] = dctx[m].data_ptr()
-                base = dqkv[m].data_ptr()
-                ab.dq[m], ab.dk[m], ab.dv[m], ab.ldg[m] = base, base + 2 * Ha[m], base + 4 * Ha[m], 3 * Ha[m]
-            self.k(ab)
-            self.put(b, L.OP_ATTN_BWD, aa, ab)
+        if need_dqkv:
+            self.gemm(b, L.NN, L.EPI_BF16, [self.prob(dd[m], self.W(names[m]["o"] + ".weight"), dctx[m], self.st[m].M, Ha[m], Hm[m], Hm[m], Ha[m], Ha[m]) for m in ms])
+            for m in ms:
+                if not (gate[0][m] or gate[1][m]):       # K/V of this modality unused: their gradient is zero
+                    self.zero(b, dqkv[m])
+            for aa, mq, gl in attn:
+                ab = L.AttnBwdArgs()
+                for m in mq:
+                    ab.dctx[m] = dctx[m].data_ptr()
+                    base = dqkv[m].data_ptr()
+                    ab.dq[m], ab.dk[m], ab.dv[m], ab.ldg[m] = base, base + 2 * Ha[m], base + 4 * Ha[m], 3 * Ha[m]
+                self.k(ab)
+                self.put(b, L.OP_ATTN_BWD, aa, ab)
         # all weight gradients of the sub-layer in ONE grouped launch (more workgroups per CU), listed in front of the Q|K|V
         # dgrad: they need dqkv, not its product, and start beside that GEMM instead of beside the next sub-layer's LayerNorm backward
         self._wgrad(b, ms, shared, [lambda m: (dd[m], ctx[m], self.G(names[m]["o"] + ".weight"), self.G(names[m]["o"] + ".bias"), Hm[m], Ha[m], Hm[m], Ha[m]),
-                                    lambda m: (dqkv[m], x_in[m], wqkv(m, "grad"), bqkv(m, "grad"), 3 * Ha[m], Hm[m], 3 * Ha[m], Hm[m])])
-        self.gemm(b, L.NN, L.EPI_ADDR, [self.prob(dqkv[m], wqkv(m, "shadow"), dxn[m], self.st[m].M, Hm[m], 3 * Ha[m], 3 * Ha[m], Hm[m], Hm[m], R=dz[m], ldr=Hm[m]) for m in ms])
+                                    lambda m: (dqkv[m], x_in[m], wqkv(m, "grad"), bqkv(m, "grad"), 3 * Ha[m], Hm[m], 3 * Ha[m], Hm[m])],
+                    [o_of, qkv_all])
+        self.gemm_kept(b, L.NN, L.EPI_ADDR, [self.prob(dqkv[m], wqkv(m, "shadow"), dxn[m], self.st[m].M, Hm[m], 3 * Ha[m], 3 * Ha[m], Hm[m], Hm[m], R=dz[m], ldr=Hm[m]) for m in ms],
+                       [live_in[m] for m in ms])
         return b
 
     def _tail_fwd(self, tag, ms, names, d, x_in, Hm):
@@ -152,16 +170,20 @@ class SublayerBuilders:
         self._ln_pair(self.fwd.ops, L.OP_LN_FWD, lnf)          # both streams in one launch when their widths agree
         return state
 
-    def _tail_bwd(self, b, state, shared):
-        """-> (dz, dd, dxn) per stream: gradients at the residual input and at d, and the buffer the last dgrad writes; dgamma / dbeta: _wgrad."""
+    def _tail_bwd(self, b, state, shared, need_dz=(True, True), skip=()):
+        """-> (dz, dd, dxn) per stream: gradients at the residual input and at d, and the buffer the last dgrad writes; dgamma / dbeta: _wgrad.
+        need_dz[m] False: nothing reads stream m's input gradient (frozen parameters), the kernel does not store dz.  Streams in `skip`
+        take no backward here at all."""
         dz, dd, dxn, lnb, par = {}, {}, {}, [], self.sub_k % 2
         for i, (m, (ln, d, mean, rstd, drop, Hm)) in enumerate(state.items()):
             M = self.st[m].M
             dxi, dxn[m] = self._dx_step(m)
+            if m in skip:
+                continue
             dz[m] = self.tmp("dz%d_%d" % (m, par), (M, Hm))
             dd[m] = self.tmp("dd%d_%d" % (m, par), (M, Hm)) if self.train else dz[m]
-            lnb.append(self.ln_bwd_args(dxi, d, mean, rstd, ln + ".weight", ln + ".bias", dz[m], dd[m] if self.train else None, M, drop,
-                                        accumulate=1 if (shared and i > 0) else 0, defer=True, H=Hm))
+            lnb.append(self.ln_bwd_args(dxi, d, mean, rstd, ln + ".weight", ln + ".bias", dz[m] if (need_dz[m] or not self.train) else None,
+                                        dd[m] if self.train else None, M, drop, accumulate=1 if (shared and i > 0) else 0, defer=True, H=Hm))
         self._ln_pair(b, L.OP_LN_BWD, lnb)
         return dz, dd, dxn
 
@@ -215,48 +237,65 @@ class SublayerBuilders:
         tail = self._tail_fwd(tag, ms, names, d, x_in, Hm)
         if self.fwd_only:
             return []
-        b = []
-        dz, dd, dxn = self._tail_bwd(b, tail, shared)
-        du, par = {}, self.sub_k % 2
+        # Frozen parameters: a feed-forward sub-layer's streams do not meet, so each one takes its backward only if it
+        # has a trainable parameter here or upstream of its input, its first dgrad only if something reads du, its last one only if
+        # something reads the input gradient.
+        live_in = list(self.live)
+        of = lambda m, *keys: [names[m][k] + s for k in keys for s in (".weight", ".bias")]
+        dead = [m for m in ms if not live_in[m] and self.prune(*of(m, "up", "down", "ln"))]
         for m in ms:
+            self.live[m] = m not in dead
+        b = []
+        dz, dd, dxn = self._tail_bwd(b, tail, shared, need_dz=live_in, skip=dead)
+        ma = [m for m in ms if m not in dead]
+        if not ma:
+            return b
+        du, par = {}, self.sub_k % 2
+        for m in ma:
             wtag = "" if Im[m] == self.I else "_%d" % Im[m]               # temporaries are shared by name: other widths get their own
             du[m] = self.tmp("du%d_%d%s" % (m, par, wtag), (self.st[m].M, Im[m]))
-        d1 = [self.prob(dd[m], self.W(names[m]["down"] + ".weight"), du[m], self.st[m].M, Im[m], Hm[m], Hm[m], Im[m], Im[m], R=gp[m], ldr=Im[m]) for m in ms]
-        d2 = [self.prob(du[m], self.W(names[m]["up"] + ".weight"), dxn[m], self.st[m].M, Hm[m], Im[m], Im[m], Hm[m], Hm[m], R=dz[m], ldr=Hm[m]) for m in ms]
-        self.gemm(b, L.NN, L.EPI_MULR, d1)
+        d1 = [self.prob(dd.get(m), self.W(names[m]["down"] + ".weight"), du.get(m), self.st[m].M, Im[m], Hm[m], Hm[m], Im[m], Im[m], R=gp[m], ldr=Im[m]) for m in ms]
+        d2 = [self.prob(du.get(m), self.W(names[m]["up"] + ".weight"), dxn[m], self.st[m].M, Hm[m], Im[m], Im[m], Hm[m], Hm[m], R=dz.get(m), ldr=Hm[m]) for m in ms]
+        self.gemm_kept(b, L.NN, L.EPI_MULR, d1, [m in ma and (live_in[m] or not self.fz(*of(m, "up"))) for m in ms])
         # The weight gradients need dd, h, du and x_in: everything but the LAST dgrad's output.  Their side-stream block is listed in front of that
         # dgrad, so that it starts beside a GEMM (two MFMA-bound launches share the chip without loss) instead of beside the LayerNorm backward
         # that follows, which it used to keep waiting for CUs (profiles/r03_experiments.md: 17.00 / 16.94 -> 16.52 / 16.54 ms per step).
-        self._wgrad(b, ms, shared, [lambda m: (dd[m], h[m], self.G(names[m]["down"] + ".weight"), self.G(names[m]["down"] + ".bias"), Hm[m], Im[m], Hm[m], Im[m]),
-                                    lambda m: (du[m], x_in[m], self.G(names[m]["up"] + ".weight"), self.G(names[m]["up"] + ".bias"), Im[m], Hm[m], Im[m], Hm[m])])
-        self.gemm(b, L.NN, L.EPI_ADDR, d2)
+        self._wgrad(b, ms, shared, [lambda m: (dd.get(m), h[m], self.G(names[m]["down"] + ".weight"), self.G(names[m]["down"] + ".bias"), Hm[m], Im[m], Hm[m], Im[m]),
+                                    lambda m: (du.get(m), x_in[m], self.G(names[m]["up"] + ".weight"), self.G(names[m]["up"] + ".bias"), Im[m], Hm[m], Im[m], Hm[m])],
+                    [lambda m: of(m, "down"), lambda m: of(m, "up")], dead=dead)
+        self.gemm_kept(b, L.NN, L.EPI_ADDR, d2, [m in ma and live_in[m] for m in ms])
         return b
 
-    def _wgrad(self, b, ms, shared, specs):
+    def _wgrad(self, b, ms, shared, specs, blocks=None, dead=()):
         """dW[Mo, No] = dY^T X (+ bias grad) for every spec and modality in ONE grouped TN launch.  The outputs are
         small (<= 3072 x 768) and the contraction (B*L rows) long, so every problem is split along K into chunks of
         ~5120 rows: each chunk is an ordinary problem writing its own fp32 slab (weights | bias), and one reduction
         pass sums the slabs into the gradient arena (plain stores: float atomics would cost 4x the slab traffic).
         This turns 36-144 long tiles into >= 256 balanced ones that take the 256x256 geometry.  Weights shared by
-        both modalities simply sum the slabs of both."""
-        jobs = []            # (dst weight grad, dst bias grad, Mo, No, [(dY, X, rows, lda, ldb), ...])
-        for spec in specs:
+        both modalities simply sum the slabs of both.
+        blocks[i](m): the parameter names spec i writes for modality m.  A problem whose block is frozen leaves the launch, with its slabs
+        and reductions (streams in `dead` have only such problems); the K-chunking and the tile geometry stay those of the whole group, so
+        that a trainable weight's summation order, and so its bits, do not depend on what else is frozen."""
+        jobs = []            # (dst weight grad, dst bias grad, Mo, No, [(dY, X, rows, lda, ldb), ...], block frozen)
+        for i, spec in enumerate(specs):
             per_w = {}
             for m in ms:
                 dY, X, gW, gB, Mo, No, lda, ldb = spec(m)
                 key = gW.data_ptr()
-                per_w.setdefault(key, (gW, gB, Mo, No, []))[4].append((dY, X, self.st[m].M, lda, ldb))
+                off = blocks is not None and self.prune(*blocks[i](m))
+                assert off or m not in dead
+                per_w.setdefault(key, (gW, gB, Mo, No, [], off))[4].append((dY, X, self.st[m].M, lda, ldb))
             jobs += list(per_w.values())
         # K-chunk length: ~5120 rows, halved (down to ~1280) while the whole group still yields fewer than 130 tiles of 256 x 256 (half the
         # CUs) -- the attention sub-layers' group ([768, 768] and [2304, 768] outputs) is 108 tiles of 150 K-steps at 5120, i.e. 42 % of the
         # CUs busy for 127 us; more, shorter chunks fill the chip, but every halving doubles the slab traffic: past half the chip it costs more
         # than the idle CUs (a threshold of 200 cut the text-only groups into 288 tiles of 40 K-steps: +0.08 ms per step)
         chunk_rows = 5120.0
-        tiles = lambda cr: sum(-(-Mo // 256) * -(-No // 256) * sum(max(1, int(round(rows / cr))) for _, _, rows, _, _ in srcs) for _, _, Mo, No, srcs in jobs)
+        tiles = lambda cr: sum(-(-Mo // 256) * -(-No // 256) * sum(max(1, int(round(rows / cr))) for _, _, rows, _, _ in srcs) for _, _, Mo, No, srcs, _ in jobs)
         while chunk_rows > 1280 and tiles(chunk_rows) < 130:     # (round 3 sweep, profiles/r03_experiments.md: 130 = half the CUs; 200 cut the text-only groups once more, +0.08 ms)
             chunk_rows /= 2
-        probs, reduces = [], []
-        for gW, gB, Mo, No, srcs in jobs:
+        probs, keep, reduces = [], [], []
+        for gW, gB, Mo, No, srcs, off in jobs:
             chunks = []
             for dY, X, rows, lda, ldb in srcs:
                 ns = max(1, int(round(rows / chunk_rows)))
@@ -264,8 +303,12 @@ class SublayerBuilders:
                 step = -(-step // 64) * 64
                 r0 = 0
                 while r0 < rows:
-                    chunks.append((dY[r0:], X[r0:], min(step, rows - r0), lda, ldb))
+                    chunks.append((None if off else dY[r0:], None if off else X[r0:], min(step, rows - r0), lda, ldb))
                     r0 += step
+            keep += [not off] * len(chunks)
+            if off:                  # listed for the group's geometry only
+                probs += [self.prob(None, None, None, Mo, No, rows, lda, ldb, No) for _, _, rows, lda, ldb in chunks]
+                continue
             if len(chunks) == 1:
                 dY, X, rows, lda, ldb = chunks[0]
                 probs.append(self.prob(dY, X, gW, Mo, No, rows, lda, ldb, No, bias_grad=gB))
@@ -278,8 +321,12 @@ class SublayerBuilders:
             reduces.append((gW, slab, stride, len(chunks), Mo * No))
             reduces.append((gB, slab[Mo * No:], stride, len(chunks), Mo))
         assert len(probs) <= 32, "too many wgrad problems in one group"
+        if not any(keep) and not self._deferred_ln:      # every block of the sub-layer is frozen: no side block, and no event for anyone to wait for
+            self._slab_cursor = 0
+            return
+        self.wgrad_recorded.add(self.sub_k)
         b.append(side_begin())
-        self.gemm(b, L.TN, L.EPI_F32, probs)
+        self.gemm_kept(b, L.TN, L.EPI_F32, probs, keep)
         # every slab sum and every deferred LayerNorm dgamma / dbeta reduction of the sub-layer in ONE launch (vk_side_tail)
         jobs = [L.TailJob(_addr(dst), None, _addr(src), None, stride, n, 0, ns, 0, 0) for dst, src, stride, ns, n in reduces]
         by_dst = {}

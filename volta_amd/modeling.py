@@ -11,6 +11,7 @@ Differences a caller can observe, all deliberate:
 """
 import logging
 import os
+import weakref
 
 import torch
 from torch import nn
@@ -227,17 +228,35 @@ class EngineHostModel(PreTrainedModel):
                 p._vk_owner = self
         return self._arena
 
+    def _frozen_signature(self, arena):
+        """The pruning decision of the parameters' current requires_grad pattern (engine.canonical_frozen): a frozenset of arena names,
+        empty when no block is frozen as a whole.  One pass over the parameters per forward; the decision of the last pattern is kept."""
+        pattern = tuple(p.requires_grad for _, p in arena.param_list())
+        memo = arena.frozen_memo
+        if memo is None or memo[0] != pattern:
+            sig = frozenset()
+            if not all(pattern):
+                from .engine import canonical_frozen
+                sig = canonical_frozen(arena, [n for (n, _), on in zip(arena.param_list(), pattern) if not on], self._heads_mode)
+            memo = arena.frozen_memo = (pattern, sig)
+        return memo[1]
+
     def _engine(self, B, T, Rv, train, task_id=None, maps=False):
         from .engine import StepEngine
         arena = self.materialize()
         key = (B, T, Rv, bool(train), self._fp8, task_id, maps)
+        # frozen parameters (requires_grad False) prune the backward list: the plan is keyed by what they prune, and by nothing more
+        # when they prune nothing -- flipping requires_grad between steps selects (or builds) the matching plan
+        frozen = self._frozen_signature(arena)
+        if frozen:
+            key += (frozen,)
         eng = self._engines.get(key)
         if eng is None:
             for k in [k for k in self._engines if k[3] == key[3] and k[5] == task_id and k[6] == maps]:      # one plan per mode (and task head) keeps memory bounded
                 del self._engines[k]
             task = (task_id, self.task_cfg[task_id]) if task_id is not None else None
             eng = StepEngine(self.config, arena, B, T, Rv, train, heads=self._heads_mode, fp8=self._fp8, task=task,
-                             task_dropout=self._task_dropout, attn_maps=maps)
+                             task_dropout=self._task_dropout, attn_maps=maps, frozen=frozen)
             self._engines[key] = eng
         return eng
 
@@ -324,6 +343,17 @@ class EngineHostModel(PreTrainedModel):
         arena = eng.arena
         from .optimization import flush_clip
         flush_clip(arena)                   # a clip coefficient no optimizer step has consumed applies to the gradients it was computed for
+        if eng.pruned:
+            ddp = self._ddp
+            if ddp is not None and ddp.reducer.mode == "zero1":
+                raise NotImplementedError("DistributedDataParallel(mode='zero1') with frozen parameters: the pruned backward list leaves gradient "
+                                          "ranges unwritten, and the sharded step walks every shard; use mode 'allreduce' or 'rs_ag'")
+            if arena.grad_plan is None or arena.grad_plan() is not eng:
+                # the ranges the pruned list never writes read zero: cleared when this plan takes over (they may hold the gradients of a step
+                # before the freeze), not every step -- gradient accumulation adds the whole arena and so keeps them at zero
+                for n in eng.pruned:
+                    arena.view(n, "grad").zero_()
+        arena.grad_plan = weakref.ref(eng)
         skip = self._torch_param_prefixes
         # frozen parameters (requires_grad False: volta/train_utils.py:250-255) get no .grad, as under autograd; the
         # optimizer and clip_grad_norm_ then leave their arena chunks alone

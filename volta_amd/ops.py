@@ -139,16 +139,29 @@ def ln_fwd(d, x, gamma, beta, y, z, mean, rstd, M, H, drop=None, split_row=None,
 
 def ln_bwd(dy, z, mean, rstd, gamma, dz, dd, partial, dgamma, dbeta, M, H, drop=None, split_row=None, post=0,
            out_scale=1.0, dyn=None, segs=None):
-    for t in (dy, z, dz):
+    check(L.lib.vk_ln_bwd(C.byref(ln_bwd_args(dy, z, mean, rstd, gamma, dz, dd, partial, dgamma, dbeta, M, H, drop, split_row, post, out_scale,
+                                              dyn, segs)), stream_ptr()))
+
+
+def ln_bwd_args(dy, z, mean, rstd, gamma, dz, dd, partial, dgamma, dbeta, M, H, drop=None, split_row=None, post=0,
+                out_scale=1.0, dyn=None, segs=None):
+    """vk_ln_bwd_args.  partial None: gamma and beta are frozen -- the launch without column sums, dgamma / dbeta ignored (may be None);
+    dz / dd None: that output is not stored."""
+    for t in (dy, z) + ((dz,) if dz is not None else ()):
         _bf16(t)
         assert t.numel() >= M * H
-    assert partial.numel() >= L.lib.vk_ln_bwd_partial_rows(M) * 2 * H and partial.dtype == torch.float32
-    assert dgamma.numel() == H and dbeta.numel() == H
+    if partial is not None:
+        assert partial.numel() >= L.lib.vk_ln_bwd_partial_rows(M) * 2 * H and partial.dtype == torch.float32
+        assert dgamma.numel() == H and dbeta.numel() == H
     drop = drop or L.dropout_cfg(None, 0, 0.0)
-    a = L.LnBwdArgs(ptr(dy), ptr(z), ptr(mean), ptr(rstd), ptr(gamma), ptr(dz), ptr(dd), ptr(partial), ptr(dgamma),
-                    ptr(dbeta), ptr(dyn), M, H, split_row if split_row is not None else M, post, out_scale, 0, drop,
-                    _segs(drop, segs))
-    check(L.lib.vk_ln_bwd(C.byref(a), stream_ptr()))
+    return L.LnBwdArgs(ptr(dy), ptr(z), ptr(mean), ptr(rstd), ptr(gamma), ptr(dz), ptr(dd), ptr(partial), ptr(dgamma),
+                       ptr(dbeta), ptr(dyn), M, H, split_row if split_row is not None else M, post, out_scale, 0, drop,
+                       _segs(drop, segs))
+
+
+def ln_bwd_pair(a, b):
+    """Two vk_ln_bwd_args jobs of equal H in one launch (two, when only one of them has parameter gradients)."""
+    check(L.lib.vk_ln_bwd_pair(C.byref(a), C.byref(b), stream_ptr()))
 
 
 def attn_args(qkv, L, masks, ctx, lse, B, nh, gate, drops=None, H=None, dh=64):
