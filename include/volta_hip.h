@@ -643,6 +643,56 @@ typedef struct vk_tail_job {
 } vk_tail_job;
 int vk_side_tail(const vk_tail_job* jobs, int njobs, vk_stream_t s);
 
+/* ------------------------------------------------------------------------------------------------
+ * Low-rank adapters (LoRA) on the columns of a fused Q|K|V projection (csrc/lora.hip).  The reference has no counterpart.  One problem
+ * is one adapter on the rows of one stream: X [M, K] bf16 (ldx), A [r, K] and B [N, r] dense bf16, and a column range [M, N] of the
+ * ldy-wide qkv (forward) / dqkv (backward) buffer.  r is 4, 8, 16 or 32 and the same in every problem of a call; K and N are multiples
+ * of 64, at most 1024; leading dimensions multiples of 8; every pointer 16-byte aligned; `dyn` (device int32 or NULL) limits the rows
+ * to min(M, *dyn).  At most VK_LORA_MAX_PROBLEMS problems per call (2 streams x 3 projections).  Rounding points:
+ *   forward    T   = bf16(sum_k X[m,k] A[j,k])                          fp32 accumulation, unscaled, stored [M, r] dense
+ *              Y   = bf16(float(Y) + scale * sum_j T[m,j] B[n,j])       reads the bf16 T it stored; Y already holds X W^T + bias
+ *   backward   dT  = bf16(scale * sum_n dY[m,n] B[n,j])                 stored [M, r] dense
+ *              dB  = scale * sum_m dY[m,n] T[m,j]                       fp32 [N, r]
+ *              dA  = sum_m dT[m,j] X[m,k]                               fp32 [r, K], reads the bf16 dT it stored
+ *              dX  = bf16(float(dX) + sum_c sum_j dT_c[m,j] A_c[j,k])   when dX != NULL; the problems c that name the same dX (the
+ *                                                                       adapters of one stream) are added in ONE read-modify-write
+ * The sums over m are deterministic: fixed blocks of VK_LORA_ROW_BLOCK rows leave partial records in `work`
+ * (vk_lora_bwd_work_bytes(), 16-byte aligned, caller-owned), which are summed in index order; no float atomics.  Problems that name the
+ * same dA / dB (one adapter shared by two streams; the later one must set `accumulate`) are summed in list order by one job;
+ * `accumulate` on the first problem of an adapter adds to what dA / dB hold. */
+#define VK_LORA_MAX_PROBLEMS 6
+#define VK_LORA_ROW_BLOCK 256
+typedef struct vk_lora_problem {
+    const void* X;
+    const void* A;
+    const void* B;
+    void* T;
+    void* Y;
+    const int32_t* dyn;
+    int32_t M, K, N, r, ldx, ldy;
+    float scale;
+    int32_t reserved_;
+} vk_lora_problem;
+typedef struct vk_lora_bwd_problem {
+    const void* X;
+    const void* A;
+    const void* B;
+    const void* T;          /* what the forward stored */
+    const void* dY;
+    void* dT;
+    void* dX;               /* NULL: the input gradient is not live */
+    float* dA;              /* dA and dB both NULL: a frozen adapter, only its share of dX is computed */
+    float* dB;
+    const int32_t* dyn;
+    int32_t M, K, N, r, ldx, ldy, lddx, accumulate;
+    float scale;
+    int32_t reserved_;
+} vk_lora_bwd_problem;
+int vk_lora_fwd(const vk_lora_problem* p, int n, vk_stream_t s);
+int vk_lora_bwd(const vk_lora_bwd_problem* p, int n, void* work, vk_stream_t s);
+/* Bytes of `work` for these problems (reads M, K, N, r only); negative on bad arguments. */
+int64_t vk_lora_bwd_work_bytes(const vk_lora_bwd_problem* p, int n);
+
 /* out[i] = a[i] * b[i] (bf16); processes rows * row_len elements where rows = min(*dyn_rows, n / row_len)
  * when dyn_rows != NULL.  (d gelu(u) = dz * gelu'(u) in the prediction-head transforms.)  n and row_len multiples of 8; a, b and
  * out 16-byte aligned (refused otherwise). */
@@ -687,7 +737,9 @@ enum {
     VK_FN_HOLD,          /* vk_hold_cus(n[0], n[1], n[2]) */
     VK_FN_GATE,          /* vk_gate_wait(p[0], p[1], n[0], p[2]) */
     VK_FN_BUMP,          /* vk_bump_u64(p[0]) */
-    VK_FN_GRAD_SEED      /* vk_grad_seed(p[0]) */
+    VK_FN_GRAD_SEED,     /* vk_grad_seed(p[0]) */
+    VK_FN_LORA_FWD,      /* vk_lora_fwd(p[0], n[0]) */
+    VK_FN_LORA_BWD       /* vk_lora_bwd(p[0], n[0], p[1]) */
 };                       /* VK_FN_POOL_FWD / VK_FN_POOL_BWD: n[3] = fusion mode (VK_FUSE_*) */
 typedef struct vk_generic_args {   /* positional arguments of the small entry points, see executor.cpp */
     int32_t fn;

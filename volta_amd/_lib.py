@@ -211,6 +211,17 @@ class TailJob(C.Structure):
 
 
 TAIL_MAX_JOBS = 16
+LORA_MAX_PROBLEMS, LORA_ROW_BLOCK = 6, 256      # VK_LORA_MAX_PROBLEMS, VK_LORA_ROW_BLOCK
+
+
+class LoraProblem(C.Structure):
+    _fields_ = [(n, c_p) for n in ("X", "A", "B", "T", "Y", "dyn")] + [(n, i32) for n in ("M", "K", "N", "r", "ldx", "ldy")] + \
+               [("scale", C.c_float), ("reserved_", i32)]
+
+
+class LoraBwdProblem(C.Structure):
+    _fields_ = [(n, c_p) for n in ("X", "A", "B", "T", "dY", "dT", "dX", "dA", "dB", "dyn")] + \
+               [(n, i32) for n in ("M", "K", "N", "r", "ldx", "ldy", "lddx", "accumulate")] + [("scale", C.c_float), ("reserved_", i32)]
 
 
 class GenericArgs(C.Structure):
@@ -226,7 +237,7 @@ class Op(C.Structure):
 (FN_CAST, FN_MEMSET, FN_LOC_FWD, FN_LOC_BWD, FN_ADD_DROPOUT, FN_COLSUM, FN_SELECT, FN_GATHER, FN_SCATTER_ADD,
  FN_LOSS_FINAL, FN_POOL_FWD, FN_POOL_BWD, FN_MASK_PREP, FN_MUL, FN_VLBERT_PREP, FN_VLBERT_MASKGRAD, FN_ROWGROUP_SUM,
  FN_RELU_BWD, FN_COPY, FN_SUM_SLABS, FN_SUM_SLABS_BF16, FN_SIDE_TAIL, FN_QUANT_ROWS, FN_CAST_FP8, FN_VIS_LOSS_FWD, FN_VIS_LOSS_BWD,
- FN_NCE_NEG, FN_TEXT_END_ROWS, FN_VLBERT_OBJ_IDS, FN_VLBERT_POSITIONS, FN_HOLD, FN_GATE, FN_BUMP, FN_GRAD_SEED) = range(1, 35)
+ FN_NCE_NEG, FN_TEXT_END_ROWS, FN_VLBERT_OBJ_IDS, FN_VLBERT_POSITIONS, FN_HOLD, FN_GATE, FN_BUMP, FN_GRAD_SEED, FN_LORA_FWD, FN_LORA_BWD) = range(1, 37)
 
 
 class AttnArgs(C.Structure):
@@ -355,6 +366,9 @@ _sig("vk_gate_value", C.c_int, c_p, C.c_uint64, C.c_int, c_p, c_p)
 _sig("vk_comm_standin", C.c_int, c_p, c_p, C.c_int64, C.c_int, C.c_int, c_p, c_p)
 _sig("vk_gemm_reserve_cus", C.c_int, C.c_int)
 _sig("vk_side_tail", C.c_int, C.POINTER(TailJob), C.c_int, c_p)
+_sig("vk_lora_fwd", C.c_int, C.POINTER(LoraProblem), C.c_int, c_p)
+_sig("vk_lora_bwd", C.c_int, C.POINTER(LoraBwdProblem), C.c_int, c_p, c_p)
+_sig("vk_lora_bwd_work_bytes", C.c_int64, C.POINTER(LoraBwdProblem), C.c_int)
 _sig("vk_run_ops", C.c_int, C.POINTER(Op), C.c_int, c_p)
 _sig("vk_run_ops_timed", C.c_int, C.POINTER(Op), C.c_int, c_p, C.POINTER(C.c_float))
 _sig("vk_ln_bwd_finalize", C.c_int, C.POINTER(LnBwdArgs), c_p)
@@ -377,6 +391,7 @@ EXPORTS = ["vk_version", "vk_device_arch", "vk_last_error", "vk_set_seed", "vk_c
            "vk_axpy_f32", "vk_sum_slabs_f32", "vk_sum_slabs_bf16", "vk_memset_async", "vk_hold_cus", "vk_gate_wait", "vk_bump_u64", "vk_store_u64", "vk_gate_value", "vk_comm_standin", "vk_gemm_reserve_cus", "vk_side_tail", "vk_run_ops", "vk_run_ops_timed", "vk_side_join", "vk_side_join_from", "vk_side_stream", "vk_side_enable", "vk_concap_batch",
            "vk_lmdb_open", "vk_lmdb_close", "vk_lmdb_entries", "vk_lmdb_first", "vk_lmdb_next", "vk_lmdb_get", "vk_concap_record_decode", "vk_concap_records_decode", "vk_b64_decode",
            "vk_wordpiece_open", "vk_wordpiece_close", "vk_wordpiece_vocab_size", "vk_wordpiece_token_id", "vk_wordpiece_encode", "vk_wordpiece_encode_batch",
+           "vk_lora_fwd", "vk_lora_bwd", "vk_lora_bwd_work_bytes",
            "vk_task_batch", "vk_task_images_stage", "vk_retrieval_ranks", "vk_retrieval_ranks_shard_rows", "vk_retrieval_ranks_shard_cols", "vk_retrieval_ranks_finish", "vk_image_means", "vk_knn_pool_work_bytes", "vk_knn_pool"]
 
 

@@ -1,0 +1,478 @@
+// Low-rank adapters on the fused Q|K|V projection (include/volta_hip.h: vk_lora_fwd / vk_lora_bwd).
+//
+// One problem is one adapter (A [r, K], B [N, r], both bf16 from the shadow arena) on the rows of one stream.  Every product here has one
+// dimension of r <= 32, so none of them fills an MFMA tile of the grouped GEMM; they are passes over X, qkv, dqkv and dxn, written as
+// vector FMA / packed-bf16 dot loops over 16-byte loads (profiles/lora.md: their times against the bytes they move).  The rounding
+// points are those of the header:
+//   forward   T = bf16(X A^T)                       rowdot      a wave per four rows, the panel A in LDS, v_dot2c_f32_bf16
+//             qkv = bf16(qkv + s T B^T)             expand      8 columns x 4 rows per lane, reads the bf16 T just stored
+//   backward  dT = bf16(s dqkv B)                   rowdot      the panel B^T in LDS
+//             dB = s dqkv^T T, dA = dT^T X          colpartial  per block of VK_LORA_ROW_BLOCK rows into the workspace, then
+//                                                   reduce      the blocks summed in index order (no float atomics: same bits every run)
+//             dxn = bf16(dxn + sum_c dT_c A_c)      expand      every adapter of a stream in ONE read-modify-write of dxn
+// Two launches forward, four backward, each over all (<= 6) problems of the call.
+#include "common.h"
+#include "../../include/volta_hip.h"
+#include "util.h"
+
+namespace vk {
+
+constexpr int LORA_MAXP = VK_LORA_MAX_PROBLEMS;
+constexpr int LORA_RB = VK_LORA_ROW_BLOCK;      // rows per partial record of dA / dB: fixed, so a gradient's bits do not depend on the other problems
+constexpr int ROWDOT_ROWS = 64;                 // rows per workgroup of rowdot (4 waves x 16 rows): amortises the panel's LDS fill
+constexpr int EXPAND_RPT = 4;                   // rows per lane of expand: a panel fragment in registers serves 4 rows
+constexpr int COLP_COLS = 64;                   // columns per workgroup of colpartial
+
+__device__ __forceinline__ int rows_of(int M, const int32_t* dyn) {
+    if (!dyn) return M;
+    const int d = *dyn;
+    return d < 0 ? 0 : (d < M ? d : M);
+}
+
+__device__ __forceinline__ void unpack8(const u32x4 v, float* f) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { f[2 * i] = __uint_as_float(v[i] << 16); f[2 * i + 1] = __uint_as_float(v[i] & 0xFFFF0000u); }
+}
+
+// JC consecutive bf16 (JC = 4: 8 bytes, JC = 8: 16 bytes) -> floats
+template <int JC>
+__device__ __forceinline__ void load_bf(const uint16_t* p, float* f) {
+    if constexpr (JC == 8) {
+        unpack8(*(const u32x4*)p, f);
+    } else {
+        const u32x2 v = *(const u32x2*)p;
+        f[0] = __uint_as_float(v[0] << 16); f[1] = __uint_as_float(v[0] & 0xFFFF0000u);
+        f[2] = __uint_as_float(v[1] << 16); f[3] = __uint_as_float(v[1] & 0xFFFF0000u);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------- rowdot
+// out[m, j] = bf16(scale * sum_k P[m, k] * Q(j, k)), j < R, k < Kc;  Q(j, k) = Q[j * qs_j + k * qs_k]
+struct RowdotJob {
+    const uint16_t* P; const uint16_t* Q; uint16_t* out; const int32_t* dyn;
+    int M, Kc, ldp, qs_j, qs_k; float scale;
+};
+struct RowdotArgs { RowdotJob job[LORA_MAXP]; int start[LORA_MAXP + 1]; int n; };
+
+// Sums V values per lane over the 64 lanes of a wave so that every sum ends up in ONE lane: at each step a lane keeps one half of its
+// values, picked by one bit of its lane number, and adds the other lane's copy of that half (V -> V / 2 values per step, V - 1 exchanges
+// in all instead of 6 V for V full wave sums).  Afterwards vals[0 .. max(1, V / 64)) hold the sums of the original values
+// idx .. idx + max(1, V / 64), in a fixed order of additions.
+template <int N, int MASK>
+__device__ __forceinline__ void lane_scatter_sum(float* vals, int lane, int& idx) {
+    if constexpr (MASK >= 1) {
+        if constexpr (N > 1) {
+            constexpr int H = N / 2;
+            const bool up = (lane & MASK) != 0;
+#pragma unroll
+            for (int v = 0; v < H; ++v) {
+                const float keep = up ? vals[v + H] : vals[v], send = up ? vals[v] : vals[v + H];
+                vals[v] = keep + __shfl_xor(send, MASK);
+            }
+            if (up) idx += H;
+            lane_scatter_sum<H, MASK / 2>(vals, lane, idx);
+        } else {
+            vals[0] += __shfl_xor(vals[0], MASK);          // fewer values than lanes: the lanes that differ in this bit share one sum
+            lane_scatter_sum<1, MASK / 2>(vals, lane, idx);
+        }
+    }
+}
+
+typedef __attribute__((ext_vector_type(2))) __bf16 bf16pair;
+__device__ __forceinline__ float dot2(uint32_t a, uint32_t b, float c) {       // c + a.lo * b.lo + a.hi * b.hi on packed bf16: v_dot2c_f32_bf16
+    return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16pair, a), __builtin_bit_cast(bf16pair, b), c, false);
+}
+
+// A wave takes 4 rows at a time: a lane holds 8 elements of each row, reads the panel's 8 elements per j from LDS once for the four rows
+// and feeds packed bf16 pairs to v_dot2c_f32_bf16 (no unpacking); the 4 R lane sums are then combined across the wave.
+template <int R>
+__global__ __launch_bounds__(256) void lora_rowdot_kernel(const RowdotArgs a) {
+    constexpr int RW = 4, V = RW * R, OWN = V / 64 > 1 ? V / 64 : 1;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    uint16_t* Qs = (uint16_t*)smem;                  // [R][Kc]
+    int p = 0;
+    while (p + 1 < a.n && (int)blockIdx.x >= a.start[p + 1]) ++p;
+    const RowdotJob& jb = a.job[p];
+    const int Kc = jb.Kc, rows = rows_of(jb.M, jb.dyn);
+    const int row0 = ((int)blockIdx.x - a.start[p]) * ROWDOT_ROWS;
+    if (row0 >= rows) return;
+    for (int i = threadIdx.x; i < R * Kc; i += 256) {
+        const int j = i / Kc, k = i - j * Kc;
+        Qs[i] = jb.Q[(size_t)j * jb.qs_j + (size_t)k * jb.qs_k];
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int row_end = row0 + ROWDOT_ROWS < rows ? row0 + ROWDOT_ROWS : rows;
+    for (int m0 = row0 + wave * RW; m0 < row_end; m0 += 4 * RW) {
+        float acc[V];
+#pragma unroll
+        for (int v = 0; v < V; ++v) acc[v] = 0.f;
+        const uint16_t* prow[RW];
+#pragma unroll
+        for (int i = 0; i < RW; ++i) prow[i] = jb.P + (size_t)(m0 + i < rows ? m0 + i : rows - 1) * jb.ldp;      // a row past the end: a valid row read, its sums not stored
+        for (int k0 = lane * 8; k0 < Kc; k0 += 512) {          // Kc is a multiple of 8: a lane's 8 elements lie inside the row
+            u32x4 x[RW];
+#pragma unroll
+            for (int i = 0; i < RW; ++i) x[i] = *(const u32x4*)(prow[i] + k0);
+#pragma unroll
+            for (int j = 0; j < R; ++j) {
+                const u32x4 q = *(const u32x4*)(Qs + j * Kc + k0);
+#pragma unroll
+                for (int i = 0; i < RW; ++i)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) acc[i * R + j] = dot2(x[i][e], q[e], acc[i * R + j]);
+            }
+        }
+        int idx = 0;
+        lane_scatter_sum<V, 32>(acc, lane, idx);
+        // value v of this lane is element idx + v of the four rows' [4][R] block, which is contiguous in the dense T
+        const bool owner = V >= 64 || (lane & (64 / V - 1)) == 0;
+        if (owner) {
+#pragma unroll
+            for (int v = 0; v < OWN; ++v)
+                if (m0 + (idx + v) / R < rows) jb.out[(size_t)m0 * R + idx + v] = f2bf(acc[v] * jb.scale);
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------- expand
+// out[m, x] = bf16(float(out[m, x]) + sum_c scale_c * sum_j T_c[m, j] * W_c(j, x)), x < ncols, over the nmem members of a job.
+// mode 0: W(j, x) = W[x * R + j] (B [N, r]);  mode 1: W(j, x) = W[j * ncols + x] (A [r, K])
+struct ExpandMember { const uint16_t* T; const uint16_t* W; float scale; int mode; };
+struct ExpandJob {
+    uint16_t* out; const int32_t* dyn; int M, ncols, ldo, nmem;
+    ExpandMember mem[3];
+};
+struct ExpandArgs { ExpandJob job[LORA_MAXP]; int start[LORA_MAXP + 1]; int n; };
+
+template <int R>
+__global__ __launch_bounds__(256) void lora_expand_kernel(const ExpandArgs a) {
+    constexpr int JC = R < 8 ? R : 8;
+    int p = 0;
+    while (p + 1 < a.n && (int)blockIdx.x >= a.start[p + 1]) ++p;
+    const ExpandJob& jb = a.job[p];
+    const int rows = rows_of(jb.M, jb.dyn), chunks = jb.ncols >> 3;
+    const long long item = (long long)((int)blockIdx.x - a.start[p]) * 256 + threadIdx.x;
+    const int rg = (int)(item / chunks), x = ((int)(item - (long long)rg * chunks)) << 3;
+    const int m0 = rg * EXPAND_RPT;
+    if (m0 >= rows) return;
+    const int nr = rows - m0 < EXPAND_RPT ? rows - m0 : EXPAND_RPT;
+    float acc[EXPAND_RPT][8];
+#pragma unroll
+    for (int i = 0; i < EXPAND_RPT; ++i)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc[i][e] = 0.f;
+    for (int c = 0; c < jb.nmem; ++c) {
+        const ExpandMember& mb = jb.mem[c];
+        float part[EXPAND_RPT][8];
+#pragma unroll
+        for (int i = 0; i < EXPAND_RPT; ++i)
+#pragma unroll
+            for (int e = 0; e < 8; ++e) part[i][e] = 0.f;
+        for (int jc = 0; jc < R; jc += JC) {
+            float w[JC][8];
+            if (mb.mode == 0) {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    float t[JC];
+                    load_bf<JC>(mb.W + (size_t)(x + e) * R + jc, t);
+#pragma unroll
+                    for (int jj = 0; jj < JC; ++jj) w[jj][e] = t[jj];
+                }
+            } else {
+#pragma unroll
+                for (int jj = 0; jj < JC; ++jj) unpack8(*(const u32x4*)(mb.W + (size_t)(jc + jj) * jb.ncols + x), w[jj]);
+            }
+#pragma unroll
+            for (int i = 0; i < EXPAND_RPT; ++i) {
+                if (i < nr) {
+                    float t[JC];
+                    load_bf<JC>(mb.T + (size_t)(m0 + i) * R + jc, t);
+#pragma unroll
+                    for (int jj = 0; jj < JC; ++jj)
+#pragma unroll
+                        for (int e = 0; e < 8; ++e) part[i][e] = __builtin_fmaf(t[jj], w[jj][e], part[i][e]);
+                }
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < EXPAND_RPT; ++i)
+#pragma unroll
+            for (int e = 0; e < 8; ++e) acc[i][e] = __builtin_fmaf(part[i][e], mb.scale, acc[i][e]);
+    }
+#pragma unroll
+    for (int i = 0; i < EXPAND_RPT; ++i) {
+        if (i < nr) {
+            uint16_t* o = jb.out + (size_t)(m0 + i) * jb.ldo + x;
+            float y[8];
+            unpack8(*(const u32x4*)o, y);
+            *(u32x4*)o = u32x4{pack2bf(y[0] + acc[i][0], y[1] + acc[i][1]), pack2bf(y[2] + acc[i][2], y[3] + acc[i][3]),
+                               pack2bf(y[4] + acc[i][4], y[5] + acc[i][5]), pack2bf(y[6] + acc[i][6], y[7] + acc[i][7])};
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------- colpartial
+// part[blk][x * xs + j * js] = sum over the rows m of block blk of P[m, x] * T[m, j]: x < ncols, j < R.  A workgroup owns 64 columns of one
+// row block; its 256 lanes are NS row slices x (8 column chunks x R/4 groups of four j), each lane sums its slice's rows, and the slices
+// are added in index order through LDS.
+struct ColpJob {
+    const uint16_t* P; const uint16_t* T; float* part; const int32_t* dyn;
+    int M, ncols, ldp, xs, js, nblk;
+};
+struct ColpArgs { ColpJob job[2 * LORA_MAXP]; int start[2 * LORA_MAXP + 1]; int n; };
+
+template <int R>
+__global__ __launch_bounds__(256) void lora_colpartial_kernel(const ColpArgs a) {
+    constexpr int JG = R / 4, TPS = 8 * JG, NS = 256 / TPS;
+    __shared__ float red[256 * 33];                 // [lane][32 (+1: the slices of one output sit 32 * TPS words apart)]
+    int p = 0;
+    while (p + 1 < a.n && (int)blockIdx.x >= a.start[p + 1]) ++p;
+    const ColpJob& jb = a.job[p];
+    const int tiles = jb.ncols / COLP_COLS;
+    const int local = (int)blockIdx.x - a.start[p];
+    const int blk = local / tiles, tile = local - blk * tiles;
+    const int rows = rows_of(jb.M, jb.dyn);
+    const int slice = threadIdx.x / TPS, t = threadIdx.x - slice * TPS;
+    const int chunk = t & 7, jg = t >> 3;
+    const int x0 = tile * COLP_COLS + chunk * 8;
+    const int row_lo = blk * LORA_RB, row_hi = row_lo + LORA_RB < rows ? row_lo + LORA_RB : rows;
+    float acc[4][8];
+#pragma unroll
+    for (int jj = 0; jj < 4; ++jj)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc[jj][e] = 0.f;
+    for (int m = row_lo + slice; m < row_hi; m += NS) {
+        float x[8], tv[4];
+        unpack8(*(const u32x4*)(jb.P + (size_t)m * jb.ldp + x0), x);
+        load_bf<4>(jb.T + (size_t)m * R + jg * 4, tv);
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj)
+#pragma unroll
+            for (int e = 0; e < 8; ++e) acc[jj][e] = __builtin_fmaf(x[e], tv[jj], acc[jj][e]);
+    }
+#pragma unroll
+    for (int jj = 0; jj < 4; ++jj)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) red[threadIdx.x * 33 + jj * 8 + e] = acc[jj][e];
+    __syncthreads();
+    float* out = jb.part + (size_t)blk * jb.ncols * R;
+    for (int o = threadIdx.x; o < TPS * 32; o += 256) {        // output o = (lane-in-slice t2, value v) of this tile
+        const int t2 = o >> 5, v = o & 31;
+        float s = 0.f;
+        for (int sl = 0; sl < NS; ++sl) s += red[(sl * TPS + t2) * 33 + v];
+        const int xcol = tile * COLP_COLS + (t2 & 7) * 8 + (v & 7), j = (t2 >> 3) * 4 + (v >> 3);
+        out[(size_t)xcol * jb.xs + (size_t)j * jb.js] = s;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------- reduce
+// dst[e] = (accumulate ? dst[e] : 0) + sum over members (scale * sum over blocks, in index order), e < n
+struct ReduceMember { const float* part; int nblk; float scale; };
+struct ReduceJob { float* dst; int n, nmem, accumulate; ReduceMember mem[2]; };
+struct ReduceArgs { ReduceJob job[2 * LORA_MAXP]; int start[2 * LORA_MAXP + 1]; int n; };
+
+__global__ __launch_bounds__(256) void lora_reduce_kernel(const ReduceArgs a) {
+    int p = 0;
+    while (p + 1 < a.n && (int)blockIdx.x >= a.start[p + 1]) ++p;
+    const ReduceJob& jb = a.job[p];
+    const int e = ((int)blockIdx.x - a.start[p]) * 256 + threadIdx.x;
+    if (e >= jb.n) return;
+    float total = jb.accumulate ? jb.dst[e] : 0.f;
+    for (int c = 0; c < jb.nmem; ++c) {
+        const ReduceMember& mb = jb.mem[c];
+        float s = 0.f;
+#pragma unroll 8
+        for (int b = 0; b < mb.nblk; ++b) s += mb.part[(size_t)b * jb.n + e];          // unrolled: eight loads in flight, the additions stay in block order
+        total += s * mb.scale;
+    }
+    jb.dst[e] = total;
+}
+
+}  // namespace vk
+
+// ================================================================================================ host
+namespace {
+
+int check_common(const char* fn, int i, int M, int K, int N, int r, int ldx, int ldy, const void* const* ptrs, int nptr) {
+    if (r != 4 && r != 8 && r != 16 && r != 32) return vk::set_error("%s: problem %d: r = %d (4, 8, 16 or 32)", fn, i, r);
+    if (M < 0) return vk::set_error("%s: problem %d: M = %d", fn, i, M);
+    if (K <= 0 || N <= 0 || K % 64 || N % 64 || K > 1024 || N > 1024)
+        return vk::set_error("%s: problem %d: K = %d, N = %d (multiples of 64, at most 1024)", fn, i, K, N);
+    if (ldx < K || ldy < N || ldx % 8 || ldy % 8) return vk::set_error("%s: problem %d: leading dimensions %d / %d (multiples of 8, >= K / N)", fn, i, ldx, ldy);
+    for (int k = 0; k < nptr; ++k) {
+        if (!ptrs[k]) return vk::set_error("%s: problem %d: NULL operand %d", fn, i, k);
+        if ((uintptr_t)ptrs[k] & 15) return vk::set_error("%s: problem %d: operand %d is not 16-byte aligned", fn, i, k);
+    }
+    return 0;
+}
+
+int nblk_of(int M) { return M > 0 ? (M + VK_LORA_ROW_BLOCK - 1) / VK_LORA_ROW_BLOCK : 0; }
+int64_t round256(int64_t v) { return (v + 255) & ~(int64_t)255; }
+
+template <typename Args, typename K4, typename K8, typename K16, typename K32>
+void launch_by_r(int r, K4 k4, K8 k8, K16 k16, K32 k32, int blocks, size_t lds, hipStream_t st, const Args& a) {
+    switch (r) {
+        case 4: hipLaunchKernelGGL(k4, dim3(blocks), dim3(256), lds, st, a); break;
+        case 8: hipLaunchKernelGGL(k8, dim3(blocks), dim3(256), lds, st, a); break;
+        case 16: hipLaunchKernelGGL(k16, dim3(blocks), dim3(256), lds, st, a); break;
+        default: hipLaunchKernelGGL(k32, dim3(blocks), dim3(256), lds, st, a);
+    }
+}
+
+int launch_rowdot(const char* fn, int r, vk::RowdotArgs& a, int maxK, hipStream_t st) {
+    int blocks = 0;
+    for (int i = 0; i < a.n; ++i) { a.start[i] = blocks; blocks += (a.job[i].M + vk::ROWDOT_ROWS - 1) / vk::ROWDOT_ROWS; }
+    a.start[a.n] = blocks;
+    if (!blocks) return 0;
+    static const hipError_t attr[4] = {
+        hipFuncSetAttribute((const void*)vk::lora_rowdot_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 1024 * 2),
+        hipFuncSetAttribute((const void*)vk::lora_rowdot_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * 1024 * 2),
+        hipFuncSetAttribute((const void*)vk::lora_rowdot_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, 16 * 1024 * 2),
+        hipFuncSetAttribute((const void*)vk::lora_rowdot_kernel<32>, hipFuncAttributeMaxDynamicSharedMemorySize, 32 * 1024 * 2)};
+    (void)attr;
+    launch_by_r(r, vk::lora_rowdot_kernel<4>, vk::lora_rowdot_kernel<8>, vk::lora_rowdot_kernel<16>, vk::lora_rowdot_kernel<32>, blocks,
+                (size_t)r * maxK * 2, st, a);
+    return vk::check_launch(fn);
+}
+
+int launch_expand(const char* fn, int r, vk::ExpandArgs& a, hipStream_t st) {
+    int64_t blocks = 0;
+    for (int i = 0; i < a.n; ++i) {
+        a.start[i] = (int)blocks;
+        const int64_t items = (int64_t)((a.job[i].M + vk::EXPAND_RPT - 1) / vk::EXPAND_RPT) * (a.job[i].ncols / 8);
+        blocks += (items + 255) / 256;
+    }
+    a.start[a.n] = (int)blocks;
+    if (!blocks) return 0;
+    if (blocks > 0x7FFFFFFF) return vk::set_error("%s: too many rows", fn);
+    launch_by_r(r, vk::lora_expand_kernel<4>, vk::lora_expand_kernel<8>, vk::lora_expand_kernel<16>, vk::lora_expand_kernel<32>, (int)blocks, 0, st, a);
+    return vk::check_launch(fn);
+}
+
+}  // namespace
+
+extern "C" int vk_lora_fwd(const vk_lora_problem* p, int n, vk_stream_t s) {
+    if (!p || n < 1 || n > VK_LORA_MAX_PROBLEMS) return vk::set_error("vk_lora_fwd: %d problems (1 .. %d)", n, VK_LORA_MAX_PROBLEMS);
+    vk::RowdotArgs rd = {};
+    vk::ExpandArgs ex = {};
+    int maxK = 0;
+    for (int i = 0; i < n; ++i) {
+        const vk_lora_problem& q = p[i];
+        const void* ptrs[5] = {q.X, q.A, q.B, q.T, q.Y};
+        if (check_common("vk_lora_fwd", i, q.M, q.K, q.N, q.r, q.ldx, q.ldy, ptrs, 5)) return -1;
+        if (q.r != p[0].r) return vk::set_error("vk_lora_fwd: problem %d: r = %d, problem 0 has %d (one rank per call)", i, q.r, p[0].r);
+        for (int k = 0; k < i; ++k)
+            if (p[k].Y == q.Y || p[k].T == q.T) return vk::set_error("vk_lora_fwd: problems %d and %d write the same T or Y", k, i);
+        rd.job[i] = vk::RowdotJob{(const uint16_t*)q.X, (const uint16_t*)q.A, (uint16_t*)q.T, q.dyn, q.M, q.K, q.ldx, q.K, 1, 1.0f};
+        vk::ExpandJob& e = ex.job[i];
+        e.out = (uint16_t*)q.Y; e.dyn = q.dyn; e.M = q.M; e.ncols = q.N; e.ldo = q.ldy; e.nmem = 1;
+        e.mem[0] = vk::ExpandMember{(const uint16_t*)q.T, (const uint16_t*)q.B, q.scale, 0};
+        if (q.K > maxK) maxK = q.K;
+    }
+    rd.n = ex.n = n;
+    if (launch_rowdot("vk_lora_fwd (T)", p[0].r, rd, maxK, (hipStream_t)s)) return -1;
+    return launch_expand("vk_lora_fwd (expand)", p[0].r, ex, (hipStream_t)s);
+}
+
+extern "C" int64_t vk_lora_bwd_work_bytes(const vk_lora_bwd_problem* p, int n) {
+    if (!p || n < 1 || n > VK_LORA_MAX_PROBLEMS) return -1;
+    int64_t total = 0;
+    for (int i = 0; i < n; ++i) {
+        if (p[i].M < 0 || p[i].K <= 0 || p[i].N <= 0 || p[i].r <= 0) return -1;
+        total += round256((int64_t)nblk_of(p[i].M) * p[i].r * ((int64_t)p[i].K + p[i].N) * 4);
+    }
+    return total > 0 ? total : 256;
+}
+
+extern "C" int vk_lora_bwd(const vk_lora_bwd_problem* p, int n, void* work, vk_stream_t s) {
+    if (!p || n < 1 || n > VK_LORA_MAX_PROBLEMS) return vk::set_error("vk_lora_bwd: %d problems (1 .. %d)", n, VK_LORA_MAX_PROBLEMS);
+    if (!work || ((uintptr_t)work & 15)) return vk::set_error("vk_lora_bwd: the workspace must be a 16-byte aligned buffer of vk_lora_bwd_work_bytes()");
+    hipStream_t st = (hipStream_t)s;
+    vk::RowdotArgs rd = {};
+    vk::ColpArgs cp = {};
+    vk::ReduceArgs re = {};
+    vk::ExpandArgs ex = {};
+    const int r = p[0].r;
+    int maxN = 0;
+    char* w = (char*)work;
+    for (int i = 0; i < n; ++i) {
+        const vk_lora_bwd_problem& q = p[i];
+        const void* ptrs[6] = {q.X, q.A, q.B, q.T, q.dY, q.dT};
+        if (check_common("vk_lora_bwd", i, q.M, q.K, q.N, q.r, q.ldx, q.ldy, ptrs, 6)) return -1;
+        if (!q.dA != !q.dB || ((uintptr_t)q.dA & 15) || ((uintptr_t)q.dB & 15))
+            return vk::set_error("vk_lora_bwd: problem %d: dA and dB are both set (16-byte aligned) or both NULL (a frozen adapter)", i);
+        if (!q.dA && !q.dX) return vk::set_error("vk_lora_bwd: problem %d has no output (dA, dB and dX are NULL)", i);
+        if (q.r != r) return vk::set_error("vk_lora_bwd: problem %d: r = %d, problem 0 has %d (one rank per call)", i, q.r, r);
+        if (q.dX && (((uintptr_t)q.dX & 15) || q.lddx < q.K || q.lddx % 8)) return vk::set_error("vk_lora_bwd: problem %d: dX alignment / lddx %d", i, q.lddx);
+        for (int k = 0; k < i; ++k)
+            if (p[k].dT == q.dT) return vk::set_error("vk_lora_bwd: problems %d and %d write the same dT", k, i);
+        rd.job[i] = vk::RowdotJob{(const uint16_t*)q.dY, (const uint16_t*)q.B, (uint16_t*)q.dT, q.dyn, q.M, q.N, q.ldy, 1, q.r, q.scale};
+        if (q.N > maxN) maxN = q.N;
+        // partial records: dB [nblk][N][r], then dA [nblk][r][K]
+        const int nblk = nblk_of(q.M);
+        float* partB = (float*)w;
+        float* partA = partB + (size_t)nblk * q.N * q.r;
+        w += round256((int64_t)nblk * q.r * ((int64_t)q.K + q.N) * 4);
+        if (q.dA) {
+        cp.job[cp.n++] = vk::ColpJob{(const uint16_t*)q.dY, (const uint16_t*)q.T, partB, q.dyn, q.M, q.N, q.ldy, q.r, 1, nblk};
+        cp.job[cp.n++] = vk::ColpJob{(const uint16_t*)q.X, (const uint16_t*)q.dT, partA, q.dyn, q.M, q.K, q.ldx, 1, q.K, nblk};
+        // gradient jobs: the problems of one adapter (a shared sub-layer's two streams) are summed by ONE job, in list order
+        int g = -1;
+        for (int k = 0; k < re.n; k += 2)
+            if (re.job[k].dst == q.dB) g = k;
+        if (g < 0) {
+            g = re.n;
+            re.n += 2;
+            re.job[g].dst = q.dB; re.job[g].n = q.N * q.r; re.job[g].accumulate = q.accumulate != 0;
+            re.job[g + 1].dst = q.dA; re.job[g + 1].n = q.r * q.K; re.job[g + 1].accumulate = q.accumulate != 0;
+        } else {
+            if (!q.accumulate) return vk::set_error("vk_lora_bwd: problem %d writes the gradients of an earlier problem without `accumulate`", i);
+            if (re.job[g + 1].dst != q.dA || re.job[g].n != q.N * q.r || re.job[g + 1].n != q.r * q.K || re.job[g].nmem >= 2)
+                return vk::set_error("vk_lora_bwd: problem %d: a shared adapter has one dA, one dB and at most two sources", i);
+        }
+        re.job[g].mem[re.job[g].nmem++] = vk::ReduceMember{partB, nblk, q.scale};
+        re.job[g + 1].mem[re.job[g + 1].nmem++] = vk::ReduceMember{partA, nblk, 1.0f};
+        }
+        if (q.dX) {
+            int e = -1;
+            for (int k = 0; k < ex.n; ++k)
+                if (ex.job[k].out == (uint16_t*)q.dX) e = k;
+            if (e < 0) {
+                e = ex.n++;
+                vk::ExpandJob& j = ex.job[e];
+                j.out = (uint16_t*)q.dX; j.dyn = q.dyn; j.M = q.M; j.ncols = q.K; j.ldo = q.lddx; j.nmem = 0;
+            }
+            vk::ExpandJob& j = ex.job[e];
+            if (j.M != q.M || j.ncols != q.K || j.ldo != q.lddx || j.dyn != q.dyn || j.nmem >= 3)
+                return vk::set_error("vk_lora_bwd: problem %d: the (at most 3) adapters that add into one dX share its shape", i);
+            j.mem[j.nmem++] = vk::ExpandMember{(const uint16_t*)q.dT, (const uint16_t*)q.A, 1.0f, 1};
+        }
+    }
+    for (int i = 0; i < n; ++i)          // no gradient may alias another job's: dA of one adapter is nobody's dB
+        for (int k = 0; k < n; ++k)
+            if (p[i].dA && p[i].dA == p[k].dB) return vk::set_error("vk_lora_bwd: dA of problem %d is dB of problem %d", i, k);
+    rd.n = n;
+    if (launch_rowdot("vk_lora_bwd (dT)", r, rd, maxN, st)) return -1;
+    {
+        int blocks = 0;
+        for (int i = 0; i < cp.n; ++i) { cp.start[i] = blocks; blocks += cp.job[i].nblk * (cp.job[i].ncols / vk::COLP_COLS); }
+        cp.start[cp.n] = blocks;
+        if (blocks) {
+            launch_by_r(r, vk::lora_colpartial_kernel<4>, vk::lora_colpartial_kernel<8>, vk::lora_colpartial_kernel<16>, vk::lora_colpartial_kernel<32>,
+                        blocks, 0, st, cp);
+            if (vk::check_launch("vk_lora_bwd (partials)")) return -1;
+        }
+    }
+    {
+        int blocks = 0;
+        for (int i = 0; i < re.n; ++i) { re.start[i] = blocks; blocks += (re.job[i].n + 255) / 256; }
+        re.start[re.n] = blocks;
+        if (blocks) {
+            hipLaunchKernelGGL(vk::lora_reduce_kernel, dim3(blocks), dim3(256), 0, st, re);
+            if (vk::check_launch("vk_lora_bwd (reduce)")) return -1;
+        }
+    }
+    if (ex.n) return launch_expand("vk_lora_bwd (dX)", r, ex, st);
+    return 0;
+}

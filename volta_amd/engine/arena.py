@@ -24,7 +24,7 @@ class ParamArena:
             group = [name]
             for q in ("query", "v_query"):
                 tag = ".attention_self.%s." % q
-                if tag in name:
+                if tag in name and name.rsplit(".", 1)[1] in ("weight", "bias"):      # not a projection's LoRA adapters: slots of their own
                     pre, suf = name.split(tag)
                     kq = q.replace("query", "")
                     group = ["%s.attention_self.%s%s.%s" % (pre, kq, k, suf) for k in ("query", "key", "value")]
@@ -66,6 +66,8 @@ class ParamArena:
         self.opt_pending = None         # (range bounds, events) of a pipelined optimizer step still in flight (optimization.py)
         self.frozen_memo = None         # (requires_grad pattern, its pruning decision) of the last forward (modeling._frozen_signature)
         self.grad_plan = None           # weak reference to the plan whose backward wrote `grad` last (modeling._backward_begin)
+        lora = getattr(model, "lora_config", None)
+        self.lora_scale = lora["alpha"] / lora["r"] if lora else None      # alpha / r of the model's LoRA adapters (volta_amd/lora.py)
 
     def view(self, name, which="master"):
         buf = getattr(self, which)

@@ -18,7 +18,8 @@ from .sublayers import SublayerBuilders
 def frozen_blocks(arena, heads="pretrain"):
     """The blocks a backward list is pruned by: [[arena names]].  A block's gradient ops are dropped when every parameter of it is frozen
     and stay as they are otherwise.  One block each: the weight and bias of a Linear (one TN problem writes both); the six Q|K|V tensors
-    of an attention sub-layer and modality (one [3 Ha, Hm] product); gamma and beta of a LayerNorm; everything under one embedding
+    of an attention sub-layer and modality (one [3 Ha, Hm] product); `lora_A` and `lora_B` of one projection (one LoRA problem writes
+    both); gamma and beta of a LayerNorm; everything under one embedding
     prefix (one backward; VisualBERT, VL-BERT and UNITER embed both modalities under one prefix).  The tied LM decoder of the pre-training
     heads writes the word table's gradient and the decoder bias in one product: there (word table, decoder bias) is a block too, and
     the word table's gradient is left alone only when both blocks it belongs to are frozen."""
@@ -33,6 +34,8 @@ def frozen_blocks(arena, heads="pretrain"):
             key = "decoder"
         else:
             key = re.sub(r"\.attention_self\.(v_)?(query|key|value)\.(weight|bias)$", r".attention_self.\1qkv", name)
+            if key == name:
+                key = re.sub(r"\.lora_[AB]$", ".lora", name)          # the adapter of one projection: a block apart from the base Q|K|V
             if key == name:
                 key = name.rsplit(".", 1)[0]
         blocks.setdefault(key, []).append(name)

@@ -60,10 +60,16 @@ class SublayerBuilders:
         qkv_names = lambda m, part: [names[m][c] + part for c in "qkv"]                 # adjacent in the arena: one [3 Ha, Hm] block
         wqkv = lambda m, which: self.arena.span(qkv_names(m, ".weight"), which, (3 * Ha[m], Hm[m]))
         bqkv = lambda m, which: self.arena.span(qkv_names(m, ".bias"), which, (3 * Ha[m],))
+        # LoRA adapters (volta_amd/lora.py): [(stream, column block 0 q | 1 k | 2 v, holder name)]; a shared sub-layer lists its one adapter per stream
+        lora = [(m, c, names[m]["qkv"[c]]) for m in ms for c in range(3) if names[m]["qkv"[c]] + ".lora_A" in self.arena.params]
+        if lora and self.fp8:
+            raise NotImplementedError("attention sub-layer %d has LoRA adapters: the fp8 (e4m3) projection path does not run them; "
+                                      "merge_lora() first or use the bf16 projections" % n)
         if self.fp8:
             self.gemm_fp8(f, L.EPI_BF16, [(x8_in[m] or x_in[m], wqkv(m, "master"), qkv[m], bqkv(m, "master"), None) for m in ms])
         else:
             self.gemm(f, L.NT, L.EPI_BF16, [self.prob(x_in[m], wqkv(m, "shadow"), qkv[m], self.st[m].M, 3 * Ha[m], Hm[m], Hm[m], Hm[m], 3 * Ha[m], bias=bqkv(m, "master")) for m in ms])
+        lora_T = self._lora_fwd(f, tag, lora, x_in, qkv, Hm, Ha) if lora else {}
         # dropout sites in the reference's call order: tt, tv, then vv, vt (encoders.py:294-295, 309-310)
         pdrop = (cfg.attention_probs_dropout_prob, cfg.v_attention_probs_dropout_prob)
         drops = {(i, j): self.drop(pdrop[i]) for i, j in ((0, 0), (0, 1), (1, 1), (1, 0)) if gate[i][j]}
@@ -119,15 +125,17 @@ class SublayerBuilders:
         qkv_all = lambda m: qkv_names(m, ".weight") + qkv_names(m, ".bias")
         ln_of = lambda m: (names[m]["ln"] + ".weight", names[m]["ln"] + ".bias")
         o_of = lambda m: (names[m]["o"] + ".weight", names[m]["o"] + ".bias")
-        if not any(live_in[m] or not self.fz(*qkv_all(m), *o_of(m), *ln_of(m)) for m in ms):
+        lora_of = lambda m: [stem + leaf for mm, _, stem in lora if mm == m for leaf in (".lora_A", ".lora_B")]      # each adapter is a block of its own
+        lora_on = lambda m: any(not self.fz(stem + ".lora_A", stem + ".lora_B") for mm, _, stem in lora if mm == m)
+        if not any(live_in[m] or lora_on(m) or not self.fz(*qkv_all(m), *o_of(m), *ln_of(m)) for m in ms):
             for m in ms:
                 self._dx_step(m)               # the ping-pong parity of dX counts every sub-layer
-                self.prune(*qkv_all(m), *o_of(m), *ln_of(m))
+                self.prune(*qkv_all(m), *o_of(m), *ln_of(m), *lora_of(m))
             return []
         for m in ms:
             self.live[m] = True
         b = []
-        need_dqkv = any(live_in[m] or not self.fz(*qkv_all(m)) for m in ms)      # else nothing reads past dd: o's weight gradient and the LayerNorm's are all
+        need_dqkv = any(live_in[m] or lora_on(m) or not self.fz(*qkv_all(m)) for m in ms)      # else nothing reads past dd: o's weight gradient and the LayerNorm's are all
         dz, dd, dxn = self._tail_bwd(b, tail, shared, need_dz=live_in)
         dctx, dqkv, par = {}, {}, self.sub_k % 2
         for m in ms:
@@ -154,7 +162,54 @@ class SublayerBuilders:
                     [o_of, qkv_all])
         self.gemm_kept(b, L.NN, L.EPI_ADDR, [self.prob(dqkv[m], wqkv(m, "shadow"), dxn[m], self.st[m].M, Hm[m], 3 * Ha[m], 3 * Ha[m], Hm[m], Hm[m], R=dz[m], ldr=Hm[m]) for m in ms],
                        [live_in[m] for m in ms])
+        if lora:         # behind the last dgrad: dqkv, x_in and T are still live, dxn[m] holds the base projection's input gradient
+            self._lora_bwd(b, lora, lora_T, x_in, dqkv, dxn, live_in, Hm, Ha)
         return b
+
+    def _lora_fwd(self, f, tag, lora, x_in, qkv, Hm, Ha):
+        """One LoRA forward op behind the Q|K|V launch: qkv columns += s (x A^T) B^T for every adapter of the active streams.  -> T per adapter
+        (kept for the backward; one shared buffer per shape in a forward-only plan)."""
+        s = self.arena.lora_scale
+        assert s is not None, "the arena holds LoRA adapters but no scale: build it from a model that add_lora() prepared"
+        probs, T = [], {}
+        for m, c, stem in lora:
+            A, Bw = self.W(stem + ".lora_A"), self.W(stem + ".lora_B")
+            r, M = A.shape[0], self.st[m].M
+            assert tuple(A.shape) == (r, Hm[m]) and tuple(Bw.shape) == (Ha[m], r), (stem, tuple(A.shape), tuple(Bw.shape))
+            T[(m, c)] = self.tmp("loraT%d%d_%d_%d" % (m, c, M, r), (M, r)) if self.fwd_only else self.buf(tag + "loraT%d%d" % (m, c), (M, r))
+            probs.append(L.LoraProblem(_addr(x_in[m]), _addr(A), _addr(Bw), _addr(T[(m, c)]), qkv[m].data_ptr() + 2 * c * Ha[m], None,
+                                       M, Hm[m], Ha[m], r, Hm[m], 3 * Ha[m], s, 0))
+        assert len(probs) <= L.LORA_MAX_PROBLEMS
+        arr = self.k((L.LoraProblem * len(probs))(*probs))
+        self.emit(f, L.FN_LORA_FWD, p=(arr,), n=(len(probs),))
+        return T
+
+    def _lora_bwd(self, b, lora, T, x_in, dqkv, dxn, live_in, Hm, Ha):
+        """One LoRA backward op: dA, dB of every trainable adapter (a frozen one is pruned, its range reads zero) and, where the input
+        gradient is live, every adapter's share of dxn -- a frozen adapter's too: the gradient passes through it.  An adapter shared by both
+        streams takes the text rows first, then the vision rows (`accumulate`), like a shared weight in _wgrad."""
+        s = self.arena.lora_scale
+        probs, written = [], set()
+        for m, c, stem in lora:
+            off = self.prune(stem + ".lora_A", stem + ".lora_B")
+            if off and not live_in[m]:
+                continue
+            A, Bw = self.W(stem + ".lora_A"), self.W(stem + ".lora_B")
+            r, M = A.shape[0], self.st[m].M
+            dT = self.tmp("loradT%d%d_%d_%d" % (m, c, M, r), (M, r))
+            gA, gB = (None, None) if off else (self.G(stem + ".lora_A"), self.G(stem + ".lora_B"))
+            probs.append(L.LoraBwdProblem(_addr(x_in[m]), _addr(A), _addr(Bw), _addr(T[(m, c)]), dqkv[m].data_ptr() + 2 * c * Ha[m], _addr(dT),
+                                          _addr(dxn[m]) if live_in[m] else None, _addr(gA), _addr(gB), None,
+                                          M, Hm[m], Ha[m], r, Hm[m], 3 * Ha[m], Hm[m], int(stem in written), s, 0))
+            if not off:
+                written.add(stem)
+        if not probs:
+            return
+        arr = self.k((L.LoraBwdProblem * len(probs))(*probs))
+        nbytes = L.lib.vk_lora_bwd_work_bytes(arr, len(probs))
+        assert nbytes > 0, "vk_lora_bwd_work_bytes refused the problems"
+        work = self.tmp("lora_work_%d" % nbytes, (nbytes,), torch.uint8)
+        self.emit(b, L.FN_LORA_BWD, p=(arr, work), n=(len(probs),))
 
     def _tail_fwd(self, tag, ms, names, d, x_in, Hm):
         """The tail both kinds of sub-layer end in: y = LayerNorm(dropout(d) + x_in) per active stream, d = the output projection's result (the

@@ -182,6 +182,7 @@ class EngineHostModel(PreTrainedModel):
     _heads_mode = "pretrain"           # StepEngine(heads=...)
     _torch_param_prefixes = ()         # parameters of torch-side head modules: autograd, not the engine, writes their gradients
     task_cfg = None
+    lora_config = None                 # volta_amd.lora.add_lora: dict(r, alpha, targets, modalities, sublayers) while the model has adapters
     # `_vk_is_model` lets clip_grad_norm_(model.parameters()) recognise the whole arena without walking it: on the instance, a nested model is none
     _ROOT_STATE = dict(_vk_is_model=True, _arena=None, _engines=None, _step=0, _seed_base=None, _last=None, _ddp=None, _fwd_serial=0,
                        _fp8=False, _task_dropout=0.1)

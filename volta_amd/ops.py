@@ -445,3 +445,74 @@ def knn_pool(X, k, shortlist=None, return_stats=False, screen_only=False):
         c, f = stats.tolist()
         return out, dict(certified=c, fallback=f)
     return out
+
+
+# ---------------------------------------------------------------------------------------------- LoRA (csrc/lora.hip)
+def _extent(t):
+    """Elements from the tensor's first one to the end of its storage."""
+    return t.untyped_storage().nbytes() // t.element_size() - t.storage_offset()
+
+
+def _lora_common(X, A, B, T, Y, M, what):
+    r, K = A.shape
+    N = B.shape[0]
+    assert r in (4, 8, 16, 32) and tuple(B.shape) == (N, r), "A [r, K] and B [N, r] with r in 4, 8, 16, 32"
+    assert K % 64 == 0 and N % 64 == 0 and K <= 1024 and N <= 1024, "K and N: multiples of 64, at most 1024"
+    for t in (X, A, B, T, Y):
+        _bf16(t)
+        assert t.data_ptr() % 16 == 0, "16-byte alignment required"
+    assert A.is_contiguous() and B.is_contiguous() and T.is_contiguous(), "A, B and T are dense"
+    ldx, ldy = X.stride(0), Y.stride(0)
+    assert X.stride(1) == 1 and Y.stride(1) == 1 and ldx % 8 == 0 and ldy % 8 == 0 and ldx >= K and ldy >= N
+    assert X.shape[1] == K and Y.shape[1] == N, "%s: X [M, K] and a [M, N] column range" % what
+    assert M <= X.shape[0] and M <= Y.shape[0] and (M == 0 or ((M - 1) * ldx + K <= _extent(X) and (M - 1) * ldy + N <= _extent(Y)))
+    assert T.numel() >= M * r
+    return r, K, N, ldx, ldy
+
+
+def lora_problem(X, A, B, T, Y, scale, M=None, dyn=None):
+    """One vk_lora_problem: Y [M, N] is a column range (a view) of the qkv buffer; T [M, r] receives bf16(X A^T)."""
+    M = X.shape[0] if M is None else M
+    r, K, N, ldx, ldy = _lora_common(X, A, B, T, Y, M, "lora_problem")
+    return L.LoraProblem(ptr(X), ptr(A), ptr(B), ptr(T), ptr(Y), ptr(dyn), M, K, N, r, ldx, ldy, float(scale), 0)
+
+
+def lora_bwd_problem(X, A, B, T, dY, dT, dX, dA, dB, scale, M=None, accumulate=False, dyn=None):
+    """One vk_lora_bwd_problem; dX None: the input gradient is not live."""
+    M = X.shape[0] if M is None else M
+    r, K, N, ldx, ldy = _lora_common(X, A, B, T, dY, M, "lora_bwd_problem")
+    _bf16(dT)
+    assert dT.is_contiguous() and dT.numel() >= M * r and dT.data_ptr() % 16 == 0
+    for g, shape in ((dA, (r, K)), (dB, (N, r))):
+        assert g.dtype == torch.float32 and g.is_cuda and g.is_contiguous() and tuple(g.shape) == shape and g.data_ptr() % 16 == 0
+    lddx = 0
+    if dX is not None:
+        _bf16(dX)
+        lddx = dX.stride(0)
+        assert dX.stride(1) == 1 and dX.shape[1] == K and lddx % 8 == 0 and lddx >= K and dX.data_ptr() % 16 == 0
+        assert M <= dX.shape[0] and (M == 0 or (M - 1) * lddx + K <= _extent(dX))
+    return L.LoraBwdProblem(ptr(X), ptr(A), ptr(B), ptr(T), ptr(dY), ptr(dT), ptr(dX), ptr(dA), ptr(dB), ptr(dyn), M, K, N, r, ldx, ldy, lddx,
+                            int(bool(accumulate)), float(scale), 0)
+
+
+def lora_fwd(problems):
+    arr = (L.LoraProblem * len(problems))(*problems)
+    check(L.lib.vk_lora_fwd(arr, len(problems), stream_ptr()))
+
+
+def lora_bwd_work(problems, device):
+    arr = (L.LoraBwdProblem * len(problems))(*problems)
+    nbytes = L.lib.vk_lora_bwd_work_bytes(arr, len(problems))
+    assert nbytes > 0, "vk_lora_bwd_work_bytes refused the problems"
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def lora_bwd(problems, work=None):
+    arr = (L.LoraBwdProblem * len(problems))(*problems)
+    need = L.lib.vk_lora_bwd_work_bytes(arr, len(problems))
+    assert need > 0, "vk_lora_bwd_work_bytes refused the problems"
+    if work is None:
+        work = torch.empty(need, dtype=torch.uint8, device="cuda")
+    assert work.numel() * work.element_size() >= need and work.data_ptr() % 16 == 0
+    check(L.lib.vk_lora_bwd(arr, len(problems), ptr(work), stream_ptr()))
+    return work
