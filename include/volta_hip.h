@@ -408,7 +408,8 @@ int vk_loss_finalize(const float* sums, const int32_t* n_t, const int32_t* n_v, 
 int vk_pool_mul_fwd(const void* pt, const void* pv, void* out, int B, int P, vk_dropout drop, vk_stream_t s);
 int vk_pool_mul_bwd(const void* dp, int ldp, const void* pt, const void* pv, void* dyt, void* dyv, int B, int P, vk_dropout drop, vk_stream_t s);
 /* The other fusions of the two pooled vectors (BertPreTrainingHeads.forward / BertForVLTasks.forward, encoders.py:766-778,1184-1195):
-   out = dropout(pt * pv | pt + pv | pt); "text" and "vl-bert_vqa" have no vision pooler (pv, dyv NULL).  vk_pool_mul_* = mode VK_FUSE_MUL. */
+   out = dropout(pt * pv | pt + pv | pt); "text" and "vl-bert_vqa" have no vision pooler (pv, dyv NULL).  vk_pool_mul_* are kernels of their own (heads.hip) that give the
+   bits of mode VK_FUSE_MUL. */
 enum { VK_FUSE_MUL = 0, VK_FUSE_SUM = 1, VK_FUSE_TEXT = 2 };
 int vk_pool_fuse_fwd(const void* pt, const void* pv, void* out, int B, int P, int mode, vk_dropout drop, vk_stream_t s);
 int vk_pool_fuse_bwd(const void* dp, int ldp, const void* pt, const void* pv, void* dyt, void* dyv, int B, int P, int mode, vk_dropout drop, vk_stream_t s);
@@ -433,6 +434,9 @@ int vk_vlbert_positions(const int64_t* ids, int B, int T, int K, int64_t* tpos, 
  *   VK_VIS_NCE    nce_2048   (:36-80)     lse_j <sample_j, x> - <sample_0, x>, sample_0 = the region's own feature,
  *                                         samples 1..n_neg = target rows neg_index[pos * n_neg + j - 1] (vk_nce_negatives)
  * The backward writes dlogits (bf16, columns [V, ldd) = 0) = d(loss_sum / max(count,1)) / d logits x *gscale.
+ * *count <= max_rows is required (vk_select_rows over the max_rows grid positions cannot give more); rows at and past *count, and
+ * everything past max_rows, are neither read nor written.  VK_VIS_XENT clamps a label outside [0, V) to the nearest class, 0 or V - 1,
+ * in the forward and in the backward alike.
  * ---------------------------------------------------------------------------------------------- */
 enum { VK_VIS_MSE = 1, VK_VIS_NCE = 2, VK_VIS_XENT = 3, VK_VIS_HUBER = 5 };
 #define VK_NCE_ACROSS 89          /* int(128 * 0.7) negatives from other images of the batch (losses.py:45) */

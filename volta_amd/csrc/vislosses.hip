@@ -95,7 +95,8 @@ __global__ __launch_bounds__(256) void vis_xent_bwd_kernel(vk_vis_loss_args a, u
     const float* x = a.logits + (size_t)i * a.ld;
     const float lse = a.lse[i];
     const int p = a.pos[i];
-    const int64_t lab = a.labels[p];
+    int64_t lab = a.labels[p];
+    lab = lab < 0 ? 0 : (lab >= a.V ? a.V - 1 : lab);      // the forward's clamp: the pair stays a loss and its gradient
     const float g = *gscale * a.weight * (a.conf ? a.conf[p] : 1.f) / (float)n;
     uint16_t* d = dlogits + (size_t)i * ldd;
     for (int c = threadIdx.x; c < ldd; c += 256) {
