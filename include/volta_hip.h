@@ -142,7 +142,12 @@ size_t vk_gemm_split_workspace_bytes(int layout, int M, int N, int nparts, int g
  * sites are the nn.Linear forwards of volta/encoders.py:242-255, 495-499, 552-565).  Layout NT only: C[M,N] = (A8[M,K] . B8[N,K]^T)
  * * scale_a[m] * scale_b[n] (+ bias, epilogue): A8 / B8 are e4m3 bytes, lda / ldb in BYTES (multiples of 16), K padded to a multiple
  * of 128 by the leading dimensions; scale vectors are the per-row de-quantisation factors written by vk_quant_rows_fp8 (NULL = 1).
- * Epilogues BF16, GELU, F32, RELU; geometry 0 (heuristic) / 128 / 256.  Gradients stay on the bf16 kernels. */
+ * Epilogues BF16, GELU, F32, RELU; geometry 0 (heuristic) / 128 / 256.  Gradients stay on the bf16 kernels.
+ * Ragged K (K % 128 != 0): the kernel contracts over whole K-steps of 128 bytes and relies on its operands for the rest.  lda must
+ * be at least round_up(K, 128) (checked) and A8's bytes in [K, round_up(K, 128)) of every row must be ZERO; the bytes of B8 that
+ * those K-steps cover -- [K, round_up(K, 128)) of each row, which with a smaller ldb runs on into the next row -- must be FINITE
+ * (anything but 0x7F / 0xFF: they are multiplied by A8's zeros).  Only what lies past byte round_up(K, 4) of the LAST row of A8
+ * (row min(*dyn, M) - 1) and of B8 (row N - 1) is never read (it reads as zero).  Nothing past column round_up(K, 128) is read. */
 #define VK_GEMM_FP8_MAX_GROUP 4
 typedef struct vk_gemm_fp8_problem {
     vk_gemm_problem p;        /* R, bias_grad unused */
@@ -154,7 +159,9 @@ typedef struct vk_gemm_fp8_problem {
 } vk_gemm_fp8_problem;
 int vk_gemm_fp8_grouped(int epilogue, const vk_gemm_fp8_problem* probs, int nprob, int geometry, vk_stream_t s);
 /* Row-wise e4m3 quantisation: scale[m] = max|x[m,:]| / 448 (1 for a zero row), dst[m,k] = rne(x[m,k] / scale[m]); src bf16 (or fp32),
- * ld / ldq in elements / bytes, K a multiple of 8 and <= 4096; dyn (device int32 or NULL) limits the rows. */
+ * ld / ldq in elements / bytes, K a multiple of 8 and <= 4096; dyn (device int32 or NULL) limits the rows.  Only dst[m, 0 .. K) and
+ * scale[m] of the rows m < min(*dyn, M) are written: the quantiser leaves dst[m, K .. ldq) as it finds it, so a caller that hands dst
+ * to vk_gemm_fp8_grouped with a ragged K zeroes that pad itself.  Source columns past K are not read. */
 int vk_quant_rows_fp8(const void* src, int src_is_f32, int64_t ld, void* dst, int64_t ldq, float* scale, int M, int K, const int32_t* dyn, vk_stream_t s);
 /* dst[i] = e4m3(saturate(src[i] * mul)), src bf16: static-scale quantisation of a whole tensor (the GELU output). */
 int vk_cast_bf16_fp8(const void* src, void* dst, int64_t n, float mul, vk_stream_t s);

@@ -125,9 +125,12 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_fp8_kernel(const KGroup8 g)
     const int K = P.K;
     if (P.dyn) { const int d = *P.dyn; M = d < M ? d : M; }
     if (m0 >= M) return;
-    // extents in BYTES (one byte per element): last valid row + valid row length, everything beyond reads as zero
-    const __amdgpu_buffer_rsrc_t rsA = make_rsrc(P.A, M > 0 ? (uint32_t)((uint32_t)(M - 1) * P.lda + K) : 0u);
-    const __amdgpu_buffer_rsrc_t rsB = make_rsrc(P.B, P.N > 0 ? (uint32_t)((uint32_t)(P.N - 1) * P.ldb + K) : 0u);
+    // extents in BYTES (one byte per element): last valid row + valid row length, everything beyond reads as zero.  The row length is
+    // rounded up to a whole dword (lda / ldb are multiples of 16, so it stays inside the row): buffer loads are range-checked per dword,
+    // and with K % 4 != 0 the dword that holds the last K % 4 bytes of the last row would end past the extent and read as zero
+    const int Kd = (K + 3) & ~3;
+    const __amdgpu_buffer_rsrc_t rsA = make_rsrc(P.A, M > 0 ? (uint32_t)((uint32_t)(M - 1) * P.lda + Kd) : 0u);
+    const __amdgpu_buffer_rsrc_t rsB = make_rsrc(P.B, P.N > 0 ? (uint32_t)((uint32_t)(P.N - 1) * P.ldb + Kd) : 0u);
 
     f32x4 acc[TI][4];
 #pragma unroll
