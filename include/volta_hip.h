@@ -704,6 +704,53 @@ int vk_lora_bwd(const vk_lora_bwd_problem* p, int n, void* work, vk_stream_t s);
 /* Bytes of `work` for these problems (reads M, K, N, r only); negative on bad arguments. */
 int64_t vk_lora_bwd_work_bytes(const vk_lora_bwd_problem* p, int n);
 
+/* ------------------------------------------------------------------------------------------------
+ * Low-rank adapters on a whole projection: the attention output and the two feed-forward projections (csrc/lora.hip).  The contract
+ * of vk_lora_fwd / vk_lora_bwd with three differences: K and N are multiples of 64, at most 4096 (the row products stage their panel in
+ * K-chunks that fit LDS and keep their accumulators across the chunks); the forward can apply the GELU; the input gradient can pass
+ * through a saved gelu'.  r is 4, 8, 16 or 32 and the same in every problem of a call; leading dimensions multiples of 8; every pointer
+ * 16-byte aligned; `dyn` limits the rows; 1 .. VK_LORA_MAX_PROBLEMS problems per call.
+ *   forward    T   = bf16(sum_k X[m,k] A[j,k])                               fp32 accumulation, stored [M, r] dense
+ *     act = 0  Y   = bf16(float(Y) + scale * sum_j T[m,j] B[n,j])            G must be NULL
+ *     act = 1  v   = float(Y) + scale * sum_j T[m,j] B[n,j]                  Y holds bf16(u), the pre-activation a VK_EPI_BF16 GEMM stored;
+ *              Y   = bf16(gelu(v)),  G = bf16(gelu'(v))                      the erf-GELU of the GEMM epilogue; G [M, N] (ldg) is required
+ *   backward   dT, dB, dA as vk_lora_bwd (same rounding points, same deterministic block partials in `work`, `accumulate` likewise)
+ *              dX  = bf16(float(dX) + rho[m,k] * sum_c sum_j dT_c[m,j] A_c[j,k])     rho = float(R[m,k]) when R != NULL (ldr), else 1:
+ *                    R is the gelu' buffer of the GEMM that produced X.  The problems c that name the same dX must name the same R and
+ *                    are added in ONE read-modify-write.
+ * Every refusal is made on the host before any launch; vk_last_error names the problem and the reason. */
+typedef struct vk_lora_proj_problem {
+    const void* X;
+    const void* A;
+    const void* B;
+    void* T;
+    void* Y;
+    void* G;                /* act = 1: receives gelu'(v); act = 0: NULL */
+    const int32_t* dyn;
+    int32_t M, K, N, r, ldx, ldy, ldg;
+    float scale;
+    int32_t act;            /* 0: Y += ...; 1: Y = gelu(Y + ...), G = gelu'(Y + ...) */
+} vk_lora_proj_problem;
+typedef struct vk_lora_proj_bwd_problem {
+    const void* X;
+    const void* A;
+    const void* B;
+    const void* T;          /* what the forward stored */
+    const void* dY;
+    void* dT;
+    void* dX;               /* NULL: the input gradient is not live */
+    float* dA;              /* dA and dB both NULL: a frozen adapter, only its share of dX is computed */
+    float* dB;
+    const void* R;          /* bf16 [M, K] (ldr) multiplied into the adapter's share of dX, or NULL */
+    const int32_t* dyn;
+    int32_t M, K, N, r, ldx, ldy, lddx, ldr, accumulate;
+    float scale;
+} vk_lora_proj_bwd_problem;
+int vk_lora_proj_fwd(const vk_lora_proj_problem* p, int n, vk_stream_t s);
+int vk_lora_proj_bwd(const vk_lora_proj_bwd_problem* p, int n, void* work, vk_stream_t s);
+/* Bytes of `work` for these problems (reads M, K, N, r only); negative on bad arguments. */
+int64_t vk_lora_proj_bwd_work_bytes(const vk_lora_proj_bwd_problem* p, int n);
+
 /* out[i] = a[i] * b[i] (bf16); processes rows * row_len elements where rows = min(*dyn_rows, n / row_len)
  * when dyn_rows != NULL.  (d gelu(u) = dz * gelu'(u) in the prediction-head transforms.)  n and row_len multiples of 8; a, b and
  * out 16-byte aligned (refused otherwise). */
@@ -750,7 +797,9 @@ enum {
     VK_FN_BUMP,          /* vk_bump_u64(p[0]) */
     VK_FN_GRAD_SEED,     /* vk_grad_seed(p[0]) */
     VK_FN_LORA_FWD,      /* vk_lora_fwd(p[0], n[0]) */
-    VK_FN_LORA_BWD       /* vk_lora_bwd(p[0], n[0], p[1]) */
+    VK_FN_LORA_BWD,      /* vk_lora_bwd(p[0], n[0], p[1]) */
+    VK_FN_LORA_PROJ_FWD, /* vk_lora_proj_fwd(p[0], n[0]) */
+    VK_FN_LORA_PROJ_BWD  /* vk_lora_proj_bwd(p[0], n[0], p[1]) */
 };                       /* VK_FN_POOL_FWD / VK_FN_POOL_BWD: n[3] = fusion mode (VK_FUSE_*) */
 typedef struct vk_generic_args {   /* positional arguments of the small entry points, see executor.cpp */
     int32_t fn;

@@ -224,6 +224,16 @@ class LoraBwdProblem(C.Structure):
                [(n, i32) for n in ("M", "K", "N", "r", "ldx", "ldy", "lddx", "accumulate")] + [("scale", C.c_float), ("reserved_", i32)]
 
 
+class LoraProjProblem(C.Structure):
+    _fields_ = [(n, c_p) for n in ("X", "A", "B", "T", "Y", "G", "dyn")] + [(n, i32) for n in ("M", "K", "N", "r", "ldx", "ldy", "ldg")] + \
+               [("scale", C.c_float), ("act", i32)]
+
+
+class LoraProjBwdProblem(C.Structure):
+    _fields_ = [(n, c_p) for n in ("X", "A", "B", "T", "dY", "dT", "dX", "dA", "dB", "R", "dyn")] + \
+               [(n, i32) for n in ("M", "K", "N", "r", "ldx", "ldy", "lddx", "ldr", "accumulate")] + [("scale", C.c_float)]
+
+
 class GenericArgs(C.Structure):
     _fields_ = [("fn", i32), ("p", c_p * 6), ("n", C.c_int64 * 6), ("f", C.c_float * 2), ("drop", Dropout)]
 
@@ -237,7 +247,8 @@ class Op(C.Structure):
 (FN_CAST, FN_MEMSET, FN_LOC_FWD, FN_LOC_BWD, FN_ADD_DROPOUT, FN_COLSUM, FN_SELECT, FN_GATHER, FN_SCATTER_ADD,
  FN_LOSS_FINAL, FN_POOL_FWD, FN_POOL_BWD, FN_MASK_PREP, FN_MUL, FN_VLBERT_PREP, FN_VLBERT_MASKGRAD, FN_ROWGROUP_SUM,
  FN_RELU_BWD, FN_COPY, FN_SUM_SLABS, FN_SUM_SLABS_BF16, FN_SIDE_TAIL, FN_QUANT_ROWS, FN_CAST_FP8, FN_VIS_LOSS_FWD, FN_VIS_LOSS_BWD,
- FN_NCE_NEG, FN_TEXT_END_ROWS, FN_VLBERT_OBJ_IDS, FN_VLBERT_POSITIONS, FN_HOLD, FN_GATE, FN_BUMP, FN_GRAD_SEED, FN_LORA_FWD, FN_LORA_BWD) = range(1, 37)
+ FN_NCE_NEG, FN_TEXT_END_ROWS, FN_VLBERT_OBJ_IDS, FN_VLBERT_POSITIONS, FN_HOLD, FN_GATE, FN_BUMP, FN_GRAD_SEED, FN_LORA_FWD, FN_LORA_BWD,
+ FN_LORA_PROJ_FWD, FN_LORA_PROJ_BWD) = range(1, 39)
 
 
 class AttnArgs(C.Structure):
@@ -369,6 +380,9 @@ _sig("vk_side_tail", C.c_int, C.POINTER(TailJob), C.c_int, c_p)
 _sig("vk_lora_fwd", C.c_int, C.POINTER(LoraProblem), C.c_int, c_p)
 _sig("vk_lora_bwd", C.c_int, C.POINTER(LoraBwdProblem), C.c_int, c_p, c_p)
 _sig("vk_lora_bwd_work_bytes", C.c_int64, C.POINTER(LoraBwdProblem), C.c_int)
+_sig("vk_lora_proj_fwd", C.c_int, C.POINTER(LoraProjProblem), C.c_int, c_p)
+_sig("vk_lora_proj_bwd", C.c_int, C.POINTER(LoraProjBwdProblem), C.c_int, c_p, c_p)
+_sig("vk_lora_proj_bwd_work_bytes", C.c_int64, C.POINTER(LoraProjBwdProblem), C.c_int)
 _sig("vk_run_ops", C.c_int, C.POINTER(Op), C.c_int, c_p)
 _sig("vk_run_ops_timed", C.c_int, C.POINTER(Op), C.c_int, c_p, C.POINTER(C.c_float))
 _sig("vk_ln_bwd_finalize", C.c_int, C.POINTER(LnBwdArgs), c_p)
@@ -391,7 +405,7 @@ EXPORTS = ["vk_version", "vk_device_arch", "vk_last_error", "vk_set_seed", "vk_c
            "vk_axpy_f32", "vk_sum_slabs_f32", "vk_sum_slabs_bf16", "vk_memset_async", "vk_hold_cus", "vk_gate_wait", "vk_bump_u64", "vk_store_u64", "vk_gate_value", "vk_comm_standin", "vk_gemm_reserve_cus", "vk_side_tail", "vk_run_ops", "vk_run_ops_timed", "vk_side_join", "vk_side_join_from", "vk_side_stream", "vk_side_enable", "vk_concap_batch",
            "vk_lmdb_open", "vk_lmdb_close", "vk_lmdb_entries", "vk_lmdb_first", "vk_lmdb_next", "vk_lmdb_get", "vk_concap_record_decode", "vk_concap_records_decode", "vk_b64_decode",
            "vk_wordpiece_open", "vk_wordpiece_close", "vk_wordpiece_vocab_size", "vk_wordpiece_token_id", "vk_wordpiece_encode", "vk_wordpiece_encode_batch",
-           "vk_lora_fwd", "vk_lora_bwd", "vk_lora_bwd_work_bytes",
+           "vk_lora_fwd", "vk_lora_bwd", "vk_lora_bwd_work_bytes", "vk_lora_proj_fwd", "vk_lora_proj_bwd", "vk_lora_proj_bwd_work_bytes",
            "vk_task_batch", "vk_task_images_stage", "vk_retrieval_ranks", "vk_retrieval_ranks_shard_rows", "vk_retrieval_ranks_shard_cols", "vk_retrieval_ranks_finish", "vk_image_means", "vk_knn_pool_work_bytes", "vk_knn_pool"]
 
 

@@ -1,4 +1,5 @@
-// Low-rank adapters on the fused Q|K|V projection (include/volta_hip.h: vk_lora_fwd / vk_lora_bwd).
+// Low-rank adapters on the fused Q|K|V projection (include/volta_hip.h: vk_lora_fwd / vk_lora_bwd) and, at the end of this file, on the
+// attention-output and feed-forward projections (vk_lora_proj_fwd / vk_lora_proj_bwd: K or N up to 4096, the GELU, a saved gelu').
 //
 // One problem is one adapter (A [r, K], B [N, r], both bf16 from the shadow arena) on the rows of one stream.  Every product here has one
 // dimension of r <= 32, so none of them fills an MFMA tile of the grouped GEMM; they are passes over X, qkv, dqkv and dxn, written as
@@ -474,5 +475,367 @@ extern "C" int vk_lora_bwd(const vk_lora_bwd_problem* p, int n, void* work, vk_s
         }
     }
     if (ex.n) return launch_expand("vk_lora_bwd (dX)", r, ex, st);
+    return 0;
+}
+
+// ================================================================================================ whole projections
+// vk_lora_proj_fwd / vk_lora_proj_bwd: adapters on the attention output and the two feed-forward projections, K or N up to 4096
+// (the feed-forward width is 3072).  colpartial, reduce and the launch helpers above serve them as they are; two kernels are new:
+//   rowdot_chunked   the row products with the panel staged in chunks of PROJ_CHUNK columns (r * 1024 * 2 bytes <= 64 KB of LDS at
+//                    r = 32) and the accumulators of every row of the workgroup kept in registers across the chunks
+//   proj_expand      expand with two optional ends: act = 1 applies the GEMM epilogue's gelu_both to Y + s T B^T and stores gelu'
+//                    non-temporally (the FFN-up adapter: its term belongs inside the GELU); rho multiplies the adapter's share of dX by
+//                    a saved gelu' (the FFN-down adapter: its input is the GELU's output)
+namespace vk {
+
+constexpr int PROJ_CHUNK = 1024;               // panel columns per LDS stage
+constexpr int PROJ_MAX_DIM = 4096;
+
+// Row groups of 4 rows per wave whose accumulators stay in registers: IT * 4 * R <= 128 floats per lane
+template <int R> struct ProjRowdot { static constexpr int IT = 32 / R > 4 ? 4 : 32 / R; static constexpr int ROWS = 16 * IT; };
+
+template <int R>
+__global__ __launch_bounds__(256) void lora_rowdot_chunked_kernel(const RowdotArgs a) {
+    constexpr int RW = 4, V = RW * R, OWN = V / 64 > 1 ? V / 64 : 1, IT = ProjRowdot<R>::IT, ROWS = ProjRowdot<R>::ROWS;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    uint16_t* Qs = (uint16_t*)smem;                  // [R][CH]
+    int p = 0;
+    while (p + 1 < a.n && (int)blockIdx.x >= a.start[p + 1]) ++p;
+    const RowdotJob& jb = a.job[p];
+    const int Kc = jb.Kc, rows = rows_of(jb.M, jb.dyn);
+    const int row0 = ((int)blockIdx.x - a.start[p]) * ROWS;
+    if (row0 >= rows) return;                        // the whole workgroup: no barrier is left waiting
+    const int CH = Kc < PROJ_CHUNK ? Kc : PROJ_CHUNK;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    float acc[IT][V];
+#pragma unroll
+    for (int it = 0; it < IT; ++it)
+#pragma unroll
+        for (int v = 0; v < V; ++v) acc[it][v] = 0.f;
+    for (int c0 = 0; c0 < Kc; c0 += CH) {
+        const int len = Kc - c0 < CH ? Kc - c0 : CH;          // a multiple of 64, like Kc
+        if (c0) __syncthreads();                              // every wave has read the previous chunk
+        for (int i = threadIdx.x; i < R * len; i += 256) {
+            const int j = i / len, k = i - j * len;
+            Qs[j * CH + k] = jb.Q[(size_t)j * jb.qs_j + (size_t)(c0 + k) * jb.qs_k];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int it = 0; it < IT; ++it) {
+            const int m0 = row0 + (it * 4 + wave) * RW;
+            if (m0 < rows) {                                  // the same for every lane of a wave
+                const uint16_t* prow[RW];
+#pragma unroll
+                for (int i = 0; i < RW; ++i) prow[i] = jb.P + (size_t)(m0 + i < rows ? m0 + i : rows - 1) * jb.ldp + c0;      // a row past the end: a valid row read, its sums not stored
+                for (int k0 = lane * 8; k0 < len; k0 += 512) {
+                    u32x4 x[RW];
+#pragma unroll
+                    for (int i = 0; i < RW; ++i) x[i] = *(const u32x4*)(prow[i] + k0);
+#pragma unroll
+                    for (int j = 0; j < R; ++j) {
+                        const u32x4 q = *(const u32x4*)(Qs + j * CH + k0);
+#pragma unroll
+                        for (int i = 0; i < RW; ++i)
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) acc[it][i * R + j] = dot2(x[i][e], q[e], acc[it][i * R + j]);
+                    }
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int it = 0; it < IT; ++it) {
+        const int m0 = row0 + (it * 4 + wave) * RW;
+        if (m0 < rows) {
+            int idx = 0;
+            lane_scatter_sum<V, 32>(acc[it], lane, idx);
+            const bool owner = V >= 64 || (lane & (64 / V - 1)) == 0;
+            if (owner) {
+#pragma unroll
+                for (int v = 0; v < OWN; ++v)
+                    if (m0 + (idx + v) / R < rows) jb.out[(size_t)m0 * R + idx + v] = f2bf(acc[it][v] * jb.scale);
+            }
+        }
+    }
+}
+
+// out[m, x] = bf16(f(float(out[m, x]) + rho[m, x] * sum_c scale_c * sum_j T_c[m, j] * W_c(j, x))): the members and modes of ExpandJob;
+// rho = 1 without `rho`; f = identity, or with `G` the GELU, whose derivative at the same argument goes to G[m, x]
+struct ProjExpandJob {
+    uint16_t* out; const int32_t* dyn; const uint16_t* rho; uint16_t* G; int M, ncols, ldo, ldr, ldg, nmem;
+    ExpandMember mem[3];
+};
+struct ProjExpandArgs { ProjExpandJob job[LORA_MAXP]; int start[LORA_MAXP + 1]; int n; };
+
+template <int R>
+__global__ __launch_bounds__(256) void lora_proj_expand_kernel(const ProjExpandArgs a) {
+    constexpr int JC = R < 8 ? R : 8;
+    int p = 0;
+    while (p + 1 < a.n && (int)blockIdx.x >= a.start[p + 1]) ++p;
+    const ProjExpandJob& jb = a.job[p];
+    const int rows = rows_of(jb.M, jb.dyn), chunks = jb.ncols >> 3;
+    const long long item = (long long)((int)blockIdx.x - a.start[p]) * 256 + threadIdx.x;
+    const int rg = (int)(item / chunks), x = ((int)(item - (long long)rg * chunks)) << 3;
+    const int m0 = rg * EXPAND_RPT;
+    if (m0 >= rows) return;
+    const int nr = rows - m0 < EXPAND_RPT ? rows - m0 : EXPAND_RPT;
+    float acc[EXPAND_RPT][8];
+#pragma unroll
+    for (int i = 0; i < EXPAND_RPT; ++i)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc[i][e] = 0.f;
+    for (int c = 0; c < jb.nmem; ++c) {
+        const ExpandMember& mb = jb.mem[c];
+        float part[EXPAND_RPT][8];
+#pragma unroll
+        for (int i = 0; i < EXPAND_RPT; ++i)
+#pragma unroll
+            for (int e = 0; e < 8; ++e) part[i][e] = 0.f;
+        for (int jc = 0; jc < R; jc += JC) {
+            float w[JC][8];
+            if (mb.mode == 0) {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    float t[JC];
+                    load_bf<JC>(mb.W + (size_t)(x + e) * R + jc, t);
+#pragma unroll
+                    for (int jj = 0; jj < JC; ++jj) w[jj][e] = t[jj];
+                }
+            } else {
+#pragma unroll
+                for (int jj = 0; jj < JC; ++jj) unpack8(*(const u32x4*)(mb.W + (size_t)(jc + jj) * jb.ncols + x), w[jj]);
+            }
+#pragma unroll
+            for (int i = 0; i < EXPAND_RPT; ++i) {
+                if (i < nr) {
+                    float t[JC];
+                    load_bf<JC>(mb.T + (size_t)(m0 + i) * R + jc, t);
+#pragma unroll
+                    for (int jj = 0; jj < JC; ++jj)
+#pragma unroll
+                        for (int e = 0; e < 8; ++e) part[i][e] = __builtin_fmaf(t[jj], w[jj][e], part[i][e]);
+                }
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < EXPAND_RPT; ++i)
+#pragma unroll
+            for (int e = 0; e < 8; ++e) acc[i][e] = __builtin_fmaf(part[i][e], mb.scale, acc[i][e]);
+    }
+#pragma unroll
+    for (int i = 0; i < EXPAND_RPT; ++i) {
+        if (i < nr) {
+            uint16_t* o = jb.out + (size_t)(m0 + i) * jb.ldo + x;
+            float y[8], v[8];
+            unpack8(*(const u32x4*)o, y);
+            if (jb.rho) {
+                float rho[8];
+                unpack8(*(const u32x4*)(jb.rho + (size_t)(m0 + i) * jb.ldr + x), rho);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) v[e] = __builtin_fmaf(rho[e], acc[i][e], y[e]);
+            } else {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) v[e] = y[e] + acc[i][e];
+            }
+            if (jb.G) {
+                float d[8];
+#pragma unroll
+                for (int e = 0; e < 8; ++e) { const float u = v[e]; gelu_both(u, v[e], d[e]); }
+                // gelu'(v) is read again only by the backward pass: non-temporal, as the GEMM epilogue stores its C2
+                __builtin_nontemporal_store(u32x4{pack2bf(d[0], d[1]), pack2bf(d[2], d[3]), pack2bf(d[4], d[5]), pack2bf(d[6], d[7])},
+                                            (u32x4*)(jb.G + (size_t)(m0 + i) * jb.ldg + x));
+            }
+            *(u32x4*)o = u32x4{pack2bf(v[0], v[1]), pack2bf(v[2], v[3]), pack2bf(v[4], v[5]), pack2bf(v[6], v[7])};
+        }
+    }
+}
+
+}  // namespace vk
+
+namespace {
+
+int proj_rowdot_rows(int r) { return r == 4 ? vk::ProjRowdot<4>::ROWS : r == 8 ? vk::ProjRowdot<8>::ROWS : r == 16 ? vk::ProjRowdot<16>::ROWS : vk::ProjRowdot<32>::ROWS; }
+
+int launch_rowdot_chunked(const char* fn, int r, vk::RowdotArgs& a, int maxK, hipStream_t st) {
+    const int per = proj_rowdot_rows(r);
+    int blocks = 0;
+    for (int i = 0; i < a.n; ++i) { a.start[i] = blocks; blocks += (a.job[i].M + per - 1) / per; }
+    a.start[a.n] = blocks;
+    if (!blocks) return 0;
+    static const hipError_t attr[4] = {
+        hipFuncSetAttribute((const void*)vk::lora_rowdot_chunked_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * vk::PROJ_CHUNK * 2),
+        hipFuncSetAttribute((const void*)vk::lora_rowdot_chunked_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * vk::PROJ_CHUNK * 2),
+        hipFuncSetAttribute((const void*)vk::lora_rowdot_chunked_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, 16 * vk::PROJ_CHUNK * 2),
+        hipFuncSetAttribute((const void*)vk::lora_rowdot_chunked_kernel<32>, hipFuncAttributeMaxDynamicSharedMemorySize, 32 * vk::PROJ_CHUNK * 2)};
+    (void)attr;
+    const int ch = maxK < vk::PROJ_CHUNK ? maxK : vk::PROJ_CHUNK;          // every job's chunk stride is min(its Kc, PROJ_CHUNK) <= this
+    launch_by_r(r, vk::lora_rowdot_chunked_kernel<4>, vk::lora_rowdot_chunked_kernel<8>, vk::lora_rowdot_chunked_kernel<16>,
+                vk::lora_rowdot_chunked_kernel<32>, blocks, (size_t)r * ch * 2, st, a);
+    return vk::check_launch(fn);
+}
+
+int launch_proj_expand(const char* fn, int r, vk::ProjExpandArgs& a, hipStream_t st) {
+    int64_t blocks = 0;
+    for (int i = 0; i < a.n; ++i) {
+        a.start[i] = (int)blocks;
+        const int64_t items = (int64_t)((a.job[i].M + vk::EXPAND_RPT - 1) / vk::EXPAND_RPT) * (a.job[i].ncols / 8);
+        blocks += (items + 255) / 256;
+    }
+    a.start[a.n] = (int)blocks;
+    if (!blocks) return 0;
+    if (blocks > 0x7FFFFFFF) return vk::set_error("%s: too many rows", fn);
+    launch_by_r(r, vk::lora_proj_expand_kernel<4>, vk::lora_proj_expand_kernel<8>, vk::lora_proj_expand_kernel<16>, vk::lora_proj_expand_kernel<32>,
+                (int)blocks, 0, st, a);
+    return vk::check_launch(fn);
+}
+
+int check_proj(const char* fn, int i, int M, int K, int N, int r, int ldx, int ldy, const void* const* ptrs, int nptr) {
+    if (r != 4 && r != 8 && r != 16 && r != 32) return vk::set_error("%s: problem %d: r = %d (4, 8, 16 or 32)", fn, i, r);
+    if (M < 0) return vk::set_error("%s: problem %d: M = %d", fn, i, M);
+    if (K <= 0 || N <= 0 || K % 64 || N % 64 || K > vk::PROJ_MAX_DIM || N > vk::PROJ_MAX_DIM)
+        return vk::set_error("%s: problem %d: K = %d, N = %d (multiples of 64, at most %d)", fn, i, K, N, vk::PROJ_MAX_DIM);
+    if (ldx < K || ldy < N || ldx % 8 || ldy % 8) return vk::set_error("%s: problem %d: leading dimensions %d / %d (multiples of 8, >= K / N)", fn, i, ldx, ldy);
+    for (int k = 0; k < nptr; ++k) {
+        if (!ptrs[k]) return vk::set_error("%s: problem %d: NULL operand %d", fn, i, k);
+        if ((uintptr_t)ptrs[k] & 15) return vk::set_error("%s: problem %d: operand %d is not 16-byte aligned", fn, i, k);
+    }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int vk_lora_proj_fwd(const vk_lora_proj_problem* p, int n, vk_stream_t s) {
+    if (!p || n < 1 || n > VK_LORA_MAX_PROBLEMS) return vk::set_error("vk_lora_proj_fwd: %d problems (1 .. %d)", n, VK_LORA_MAX_PROBLEMS);
+    vk::RowdotArgs rd = {};
+    vk::ProjExpandArgs ex = {};
+    int maxK = 0;
+    for (int i = 0; i < n; ++i) {
+        const vk_lora_proj_problem& q = p[i];
+        const void* ptrs[5] = {q.X, q.A, q.B, q.T, q.Y};
+        if (check_proj("vk_lora_proj_fwd", i, q.M, q.K, q.N, q.r, q.ldx, q.ldy, ptrs, 5)) return -1;
+        if (q.r != p[0].r) return vk::set_error("vk_lora_proj_fwd: problem %d: r = %d, problem 0 has %d (one rank per call)", i, q.r, p[0].r);
+        if (q.act != 0 && q.act != 1) return vk::set_error("vk_lora_proj_fwd: problem %d: act = %d (0 or 1)", i, q.act);
+        if (q.act == 0 && q.G) return vk::set_error("vk_lora_proj_fwd: problem %d: act = 0 takes no G", i);
+        if (q.act == 1 && (!q.G || ((uintptr_t)q.G & 15) || q.ldg < q.N || q.ldg % 8))
+            return vk::set_error("vk_lora_proj_fwd: problem %d: act = 1 needs G (16-byte aligned, ldg %d a multiple of 8, >= N)", i, q.ldg);
+        for (int k = 0; k < i; ++k)
+            if (p[k].Y == q.Y || p[k].T == q.T || (q.G && p[k].G == q.G))
+                return vk::set_error("vk_lora_proj_fwd: problems %d and %d write the same T, Y or G", k, i);
+        rd.job[i] = vk::RowdotJob{(const uint16_t*)q.X, (const uint16_t*)q.A, (uint16_t*)q.T, q.dyn, q.M, q.K, q.ldx, q.K, 1, 1.0f};
+        vk::ProjExpandJob& e = ex.job[i];
+        e.out = (uint16_t*)q.Y; e.dyn = q.dyn; e.rho = nullptr; e.G = (uint16_t*)q.G; e.M = q.M; e.ncols = q.N; e.ldo = q.ldy; e.ldr = 0; e.ldg = q.ldg;
+        e.nmem = 1;
+        e.mem[0] = vk::ExpandMember{(const uint16_t*)q.T, (const uint16_t*)q.B, q.scale, 0};
+        if (q.K > maxK) maxK = q.K;
+    }
+    rd.n = ex.n = n;
+    if (launch_rowdot_chunked("vk_lora_proj_fwd (T)", p[0].r, rd, maxK, (hipStream_t)s)) return -1;
+    return launch_proj_expand("vk_lora_proj_fwd (expand)", p[0].r, ex, (hipStream_t)s);
+}
+
+extern "C" int64_t vk_lora_proj_bwd_work_bytes(const vk_lora_proj_bwd_problem* p, int n) {
+    if (!p || n < 1 || n > VK_LORA_MAX_PROBLEMS) return -1;
+    int64_t total = 0;
+    for (int i = 0; i < n; ++i) {
+        if (p[i].M < 0 || p[i].K <= 0 || p[i].N <= 0 || p[i].r <= 0) return -1;
+        total += round256((int64_t)nblk_of(p[i].M) * p[i].r * ((int64_t)p[i].K + p[i].N) * 4);
+    }
+    return total > 0 ? total : 256;
+}
+
+extern "C" int vk_lora_proj_bwd(const vk_lora_proj_bwd_problem* p, int n, void* work, vk_stream_t s) {
+    const char* fn = "vk_lora_proj_bwd";
+    if (!p || n < 1 || n > VK_LORA_MAX_PROBLEMS) return vk::set_error("%s: %d problems (1 .. %d)", fn, n, VK_LORA_MAX_PROBLEMS);
+    if (!work || ((uintptr_t)work & 15)) return vk::set_error("%s: the workspace must be a 16-byte aligned buffer of vk_lora_proj_bwd_work_bytes()", fn);
+    hipStream_t st = (hipStream_t)s;
+    vk::RowdotArgs rd = {};
+    vk::ColpArgs cp = {};
+    vk::ReduceArgs re = {};
+    vk::ProjExpandArgs ex = {};
+    const int r = p[0].r;
+    int maxN = 0;
+    char* w = (char*)work;
+    for (int i = 0; i < n; ++i) {
+        const vk_lora_proj_bwd_problem& q = p[i];
+        const void* ptrs[6] = {q.X, q.A, q.B, q.T, q.dY, q.dT};
+        if (check_proj(fn, i, q.M, q.K, q.N, q.r, q.ldx, q.ldy, ptrs, 6)) return -1;
+        if (!q.dA != !q.dB || ((uintptr_t)q.dA & 15) || ((uintptr_t)q.dB & 15))
+            return vk::set_error("%s: problem %d: dA and dB are both set (16-byte aligned) or both NULL (a frozen adapter)", fn, i);
+        if (!q.dA && !q.dX) return vk::set_error("%s: problem %d has no output (dA, dB and dX are NULL)", fn, i);
+        if (q.r != r) return vk::set_error("%s: problem %d: r = %d, problem 0 has %d (one rank per call)", fn, i, q.r, r);
+        if (q.dX && (((uintptr_t)q.dX & 15) || q.lddx < q.K || q.lddx % 8)) return vk::set_error("%s: problem %d: dX alignment / lddx %d", fn, i, q.lddx);
+        if (q.R && (((uintptr_t)q.R & 15) || q.ldr < q.K || q.ldr % 8)) return vk::set_error("%s: problem %d: R alignment / ldr %d", fn, i, q.ldr);
+        for (int k = 0; k < i; ++k)
+            if (p[k].dT == q.dT) return vk::set_error("%s: problems %d and %d write the same dT", fn, k, i);
+        rd.job[i] = vk::RowdotJob{(const uint16_t*)q.dY, (const uint16_t*)q.B, (uint16_t*)q.dT, q.dyn, q.M, q.N, q.ldy, 1, q.r, q.scale};
+        if (q.N > maxN) maxN = q.N;
+        // partial records: dB [nblk][N][r], then dA [nblk][r][K]
+        const int nblk = nblk_of(q.M);
+        float* partB = (float*)w;
+        float* partA = partB + (size_t)nblk * q.N * q.r;
+        w += round256((int64_t)nblk * q.r * ((int64_t)q.K + q.N) * 4);
+        if (q.dA) {
+            cp.job[cp.n++] = vk::ColpJob{(const uint16_t*)q.dY, (const uint16_t*)q.T, partB, q.dyn, q.M, q.N, q.ldy, q.r, 1, nblk};
+            cp.job[cp.n++] = vk::ColpJob{(const uint16_t*)q.X, (const uint16_t*)q.dT, partA, q.dyn, q.M, q.K, q.ldx, 1, q.K, nblk};
+            // gradient jobs: the problems of one adapter (a shared sub-layer's two streams) are summed by ONE job, in list order
+            int g = -1;
+            for (int k = 0; k < re.n; k += 2)
+                if (re.job[k].dst == q.dB) g = k;
+            if (g < 0) {
+                g = re.n;
+                re.n += 2;
+                re.job[g].dst = q.dB; re.job[g].n = q.N * q.r; re.job[g].accumulate = q.accumulate != 0;
+                re.job[g + 1].dst = q.dA; re.job[g + 1].n = q.r * q.K; re.job[g + 1].accumulate = q.accumulate != 0;
+            } else {
+                if (!q.accumulate) return vk::set_error("%s: problem %d writes the gradients of an earlier problem without `accumulate`", fn, i);
+                if (re.job[g + 1].dst != q.dA || re.job[g].n != q.N * q.r || re.job[g + 1].n != q.r * q.K || re.job[g].nmem >= 2)
+                    return vk::set_error("%s: problem %d: a shared adapter has one dA, one dB and at most two sources", fn, i);
+            }
+            re.job[g].mem[re.job[g].nmem++] = vk::ReduceMember{partB, nblk, q.scale};
+            re.job[g + 1].mem[re.job[g + 1].nmem++] = vk::ReduceMember{partA, nblk, 1.0f};
+        }
+        if (q.dX) {
+            int e = -1;
+            for (int k = 0; k < ex.n; ++k)
+                if (ex.job[k].out == (uint16_t*)q.dX) e = k;
+            if (e < 0) {
+                e = ex.n++;
+                vk::ProjExpandJob& j = ex.job[e];
+                j.out = (uint16_t*)q.dX; j.dyn = q.dyn; j.rho = (const uint16_t*)q.R; j.G = nullptr; j.M = q.M; j.ncols = q.K; j.ldo = q.lddx;
+                j.ldr = q.R ? q.ldr : 0; j.ldg = 0; j.nmem = 0;
+            }
+            vk::ProjExpandJob& j = ex.job[e];
+            if (j.rho != (const uint16_t*)q.R || (q.R && j.ldr != q.ldr))
+                return vk::set_error("%s: problem %d: the adapters that add into one dX name one R (and ldr)", fn, i);
+            if (j.M != q.M || j.ncols != q.K || j.ldo != q.lddx || j.dyn != q.dyn || j.nmem >= 3)
+                return vk::set_error("%s: problem %d: the (at most 3) adapters that add into one dX share its shape", fn, i);
+            j.mem[j.nmem++] = vk::ExpandMember{(const uint16_t*)q.dT, (const uint16_t*)q.A, 1.0f, 1};
+        }
+    }
+    for (int i = 0; i < n; ++i)          // no gradient may alias another job's: dA of one adapter is nobody's dB
+        for (int k = 0; k < n; ++k)
+            if (p[i].dA && p[i].dA == p[k].dB) return vk::set_error("%s: dA of problem %d is dB of problem %d", fn, i, k);
+    rd.n = n;
+    if (launch_rowdot_chunked("vk_lora_proj_bwd (dT)", r, rd, maxN, st)) return -1;
+    {
+        int blocks = 0;
+        for (int i = 0; i < cp.n; ++i) { cp.start[i] = blocks; blocks += cp.job[i].nblk * (cp.job[i].ncols / vk::COLP_COLS); }
+        cp.start[cp.n] = blocks;
+        if (blocks) {
+            launch_by_r(r, vk::lora_colpartial_kernel<4>, vk::lora_colpartial_kernel<8>, vk::lora_colpartial_kernel<16>, vk::lora_colpartial_kernel<32>,
+                        blocks, 0, st, cp);
+            if (vk::check_launch("vk_lora_proj_bwd (partials)")) return -1;
+        }
+    }
+    {
+        int blocks = 0;
+        for (int i = 0; i < re.n; ++i) { re.start[i] = blocks; blocks += (re.job[i].n + 255) / 256; }
+        re.start[re.n] = blocks;
+        if (blocks) {
+            hipLaunchKernelGGL(vk::lora_reduce_kernel, dim3(blocks), dim3(256), 0, st, re);
+            if (vk::check_launch("vk_lora_proj_bwd (reduce)")) return -1;
+        }
+    }
+    if (ex.n) return launch_proj_expand("vk_lora_proj_bwd (dX)", r, ex, st);
     return 0;
 }

@@ -62,7 +62,9 @@ class SublayerBuilders:
         bqkv = lambda m, which: self.arena.span(qkv_names(m, ".bias"), which, (3 * Ha[m],))
         # LoRA adapters (volta_amd/lora.py): [(stream, column block 0 q | 1 k | 2 v, holder name)]; a shared sub-layer lists its one adapter per stream
         lora = [(m, c, names[m]["qkv"[c]]) for m in ms for c in range(3) if names[m]["qkv"[c]] + ".lora_A" in self.arena.params]
-        if lora and self.fp8:
+        # the output projection's adapter (target "attn_out"): [(stream, holder name)], one whole-projection LoRA problem per stream
+        lora_o = [(m, names[m]["o"]) for m in ms if names[m]["o"] + ".lora_A" in self.arena.params]
+        if (lora or lora_o) and self.fp8:
             raise NotImplementedError("attention sub-layer %d has LoRA adapters: the fp8 (e4m3) projection path does not run them; "
                                       "merge_lora() first or use the bf16 projections" % n)
         if self.fp8:
@@ -114,6 +116,8 @@ class SublayerBuilders:
             self.put(f, L.OP_ATTN_FWD, aa)
             attn.append((aa, mq, gl))
         self.gemm(f, L.NT, L.EPI_BF16, [self.prob(ctx[m], self.W(names[m]["o"] + ".weight"), d[m], self.st[m].M, Hm[m], Ha[m], Ha[m], Ha[m], Hm[m], bias=self.Pm(names[m]["o"] + ".bias")) for m in ms])
+        if lora_o:       # behind the output projection, in front of the tail: d += s (ctx A^T) B^T
+            To = self._lora_proj_fwd(f, tag, "o", [(m, stem, ctx[m], d[m], None) for m, stem in lora_o])
         tail = self._tail_fwd(tag, ms, names, d, x_in, Hm)
         if self.fwd_only:
             return []
@@ -127,10 +131,12 @@ class SublayerBuilders:
         o_of = lambda m: (names[m]["o"] + ".weight", names[m]["o"] + ".bias")
         lora_of = lambda m: [stem + leaf for mm, _, stem in lora if mm == m for leaf in (".lora_A", ".lora_B")]      # each adapter is a block of its own
         lora_on = lambda m: any(not self.fz(stem + ".lora_A", stem + ".lora_B") for mm, _, stem in lora if mm == m)
-        if not any(live_in[m] or lora_on(m) or not self.fz(*qkv_all(m), *o_of(m), *ln_of(m)) for m in ms):
+        lora_o_of = lambda m: [stem + leaf for mm, stem in lora_o if mm == m for leaf in (".lora_A", ".lora_B")]
+        lora_o_on = lambda m: any(not self.fz(stem + ".lora_A", stem + ".lora_B") for mm, stem in lora_o if mm == m)      # a trainable parameter of the sub-layer; dqkv is not its business
+        if not any(live_in[m] or lora_on(m) or lora_o_on(m) or not self.fz(*qkv_all(m), *o_of(m), *ln_of(m)) for m in ms):
             for m in ms:
                 self._dx_step(m)               # the ping-pong parity of dX counts every sub-layer
-                self.prune(*qkv_all(m), *o_of(m), *ln_of(m), *lora_of(m))
+                self.prune(*qkv_all(m), *o_of(m), *ln_of(m), *lora_of(m), *lora_o_of(m))
             return []
         for m in ms:
             self.live[m] = True
@@ -144,6 +150,9 @@ class SublayerBuilders:
             dqkv[m] = self.tmp("dqkv%d_%d%s" % (m, par, wtag), (self.st[m].M, 3 * Ha[m]))
         if need_dqkv:
             self.gemm(b, L.NN, L.EPI_BF16, [self.prob(dd[m], self.W(names[m]["o"] + ".weight"), dctx[m], self.st[m].M, Ha[m], Hm[m], Hm[m], Ha[m], Ha[m]) for m in ms])
+        if lora_o:       # directly behind the dd W_o dgrad: the attention backward reads the dctx this op adds to; without dqkv only dA and dB
+            self._lora_proj_bwd(b, [(m, stem, ctx[m], To[m], dd[m], dctx[m] if need_dqkv else None, None) for m, stem in lora_o])
+        if need_dqkv:
             for m in ms:
                 if not (gate[0][m] or gate[1][m]):       # K/V of this modality unused: their gradient is zero
                     self.zero(b, dqkv[m])
@@ -211,6 +220,52 @@ class SublayerBuilders:
         work = self.tmp("lora_work_%d" % nbytes, (nbytes,), torch.uint8)
         self.emit(b, L.FN_LORA_BWD, p=(arr, work), n=(len(probs),))
 
+    def _lora_proj_fwd(self, f, tag, which, items):
+        """One whole-projection LoRA forward op (vk_lora_proj_fwd).  items: [(stream, holder name, X [M, K], Y [M, N], G or None)]; G None:
+        Y += s (X A^T) B^T; G: Y = gelu(Y + ...), G = gelu'(Y + ...).  -> T per stream (kept for the backward; one shared buffer per
+        shape in a forward-only plan)."""
+        s = self.arena.lora_scale
+        assert s is not None, "the arena holds LoRA adapters but no scale: build it from a model that add_lora() prepared"
+        probs, T = [], {}
+        for m, stem, X, Y, G in items:
+            A, Bw = self.W(stem + ".lora_A"), self.W(stem + ".lora_B")
+            r, M, K, N = A.shape[0], self.st[m].M, X.shape[1], Y.shape[1]
+            assert tuple(A.shape) == (r, K) and tuple(Bw.shape) == (N, r) and X.shape[0] == Y.shape[0] == M, (stem, tuple(A.shape), tuple(Bw.shape))
+            T[m] = self.tmp("loraT%s%d_%d_%d" % (which, m, M, r), (M, r)) if self.fwd_only else self.buf(tag + "loraT%s%d" % (which, m), (M, r))
+            probs.append(L.LoraProjProblem(_addr(X), _addr(A), _addr(Bw), _addr(T[m]), _addr(Y), _addr(G), None, M, K, N, r, X.stride(0), Y.stride(0),
+                                           G.stride(0) if G is not None else 0, s, int(G is not None)))
+        arr = self.k((L.LoraProjProblem * len(probs))(*probs))
+        self.emit(f, L.FN_LORA_PROJ_FWD, p=(arr,), n=(len(probs),))
+        return T
+
+    def _lora_proj_bwd(self, b, items):
+        """One whole-projection LoRA backward op (vk_lora_proj_bwd).  items: [(stream, holder name, X, T, dY, dX or None, R or None)]: dA, dB
+        of every trainable adapter (a frozen one is pruned, its range reads zero) and, where dX is given, the adapter's share of the input
+        gradient, times R -- a frozen adapter's too: the gradient passes through it.  An adapter shared by both streams takes the text rows
+        first, then the vision rows (`accumulate`)."""
+        s = self.arena.lora_scale
+        probs, written = [], set()
+        for m, stem, X, T, dY, dX, R in items:
+            off = self.prune(stem + ".lora_A", stem + ".lora_B")
+            if off and dX is None:
+                continue
+            A, Bw = self.W(stem + ".lora_A"), self.W(stem + ".lora_B")
+            r, M, K, N = A.shape[0], self.st[m].M, X.shape[1], dY.shape[1]
+            dT = self.tmp("loradTp%d_%d_%d" % (m, M, r), (M, r))
+            gA, gB = (None, None) if off else (self.G(stem + ".lora_A"), self.G(stem + ".lora_B"))
+            probs.append(L.LoraProjBwdProblem(_addr(X), _addr(A), _addr(Bw), _addr(T), _addr(dY), _addr(dT), _addr(dX), _addr(gA), _addr(gB), _addr(R), None,
+                                              M, K, N, r, X.stride(0), dY.stride(0), dX.stride(0) if dX is not None else 0,
+                                              R.stride(0) if R is not None else 0, int(stem in written), s))
+            if not off:
+                written.add(stem)
+        if not probs:
+            return
+        arr = self.k((L.LoraProjBwdProblem * len(probs))(*probs))
+        nbytes = L.lib.vk_lora_proj_bwd_work_bytes(arr, len(probs))
+        assert nbytes > 0, "vk_lora_proj_bwd_work_bytes refused the problems"
+        work = self.tmp("lora_work_%d" % nbytes, (nbytes,), torch.uint8)
+        self.emit(b, L.FN_LORA_PROJ_BWD, p=(arr, work), n=(len(probs),))
+
     def _tail_fwd(self, tag, ms, names, d, x_in, Hm):
         """The tail both kinds of sub-layer end in: y = LayerNorm(dropout(d) + x_in) per active stream, d = the output projection's result (the
         LayerNorm leaves its pre-normalisation input there for the backward).  -> state for _tail_bwd."""
@@ -271,6 +326,12 @@ class SublayerBuilders:
         h = {m: self.buf(tag + "h%d" % m, (self.st[m].M, Im[m])) for m in ms}
         gp = {m: self.buf(tag + "gp%d" % m, (self.st[m].M, Im[m])) for m in ms}
         d = {m: self.buf(tag + "z%d" % m, (self.st[m].M, Hm[m])) for m in ms}
+        # adapters on the two projections (targets "ffn_up", "ffn_down"): {stream: holder name}
+        lora_up = {m: names[m]["up"] for m in ms if names[m]["up"] + ".lora_A" in self.arena.params}
+        lora_dn = {m: names[m]["down"] for m in ms if names[m]["down"] + ".lora_A" in self.arena.params}
+        if (lora_up or lora_dn) and self.fp8:
+            raise NotImplementedError("feed-forward sub-layer %d has LoRA adapters: the fp8 (e4m3) projection path does not run them; "
+                                      "merge_lora() first or use the bf16 projections" % n)
         if self.fp8:
             # the GELU output also leaves the epilogue as e4m3 with one static scale (the FFN-down projection's A operand), de-quantised
             # there through scale_a = 1 / multiplier
@@ -287,8 +348,21 @@ class SublayerBuilders:
         else:
             up = [self.prob(x_in[m], self.W(names[m]["up"] + ".weight"), h[m], self.st[m].M, Im[m], Hm[m], Hm[m], Hm[m], Im[m], bias=self.Pm(names[m]["up"] + ".bias"), C2=gp[m]) for m in ms]
             down = [self.prob(h[m], self.W(names[m]["down"] + ".weight"), d[m], self.st[m].M, Hm[m], Im[m], Im[m], Im[m], Hm[m], bias=self.Pm(names[m]["down"] + ".bias")) for m in ms]
-            self.gemm(f, L.NT, L.EPI_GELU, up)
+            if not lora_up:
+                self.gemm(f, L.NT, L.EPI_GELU, up)
+            else:
+                # A stream with an FFN-up adapter: its term belongs inside the GELU, and the GELU epilogue never stores the pre-activation.
+                # That stream's product leaves a plain launch as bf16(u) in h[m]; the adapter's op adds its term and applies the GELU there,
+                # writing h[m] and gp[m].  A stream without one keeps the GELU epilogue, in a launch of its own.
+                rest = [q for m, q in zip(ms, up) if m not in lora_up]
+                if rest:
+                    self.gemm(f, L.NT, L.EPI_GELU, rest)
+                self.gemm(f, L.NT, L.EPI_BF16, [self.prob(x_in[m], self.W(names[m]["up"] + ".weight"), h[m], self.st[m].M, Im[m], Hm[m], Hm[m], Hm[m], Im[m],
+                                                          bias=self.Pm(names[m]["up"] + ".bias")) for m in ms if m in lora_up])
+                Tup = self._lora_proj_fwd(f, tag, "up", [(m, lora_up[m], x_in[m], h[m], gp[m]) for m in ms if m in lora_up])
             self.gemm(f, L.NT, L.EPI_BF16, down)
+            if lora_dn:
+                Tdn = self._lora_proj_fwd(f, tag, "dn", [(m, lora_dn[m], h[m], d[m], None) for m in ms if m in lora_dn])
         tail = self._tail_fwd(tag, ms, names, d, x_in, Hm)
         if self.fwd_only:
             return []
@@ -297,7 +371,11 @@ class SublayerBuilders:
         # something reads the input gradient.
         live_in = list(self.live)
         of = lambda m, *keys: [names[m][k] + s for k in keys for s in (".weight", ".bias")]
-        dead = [m for m in ms if not live_in[m] and self.prune(*of(m, "up", "down", "ln"))]
+        leaves = lambda stem: (stem + ".lora_A", stem + ".lora_B")
+        ad_on = lambda which, m: m in which and not self.fz(*leaves(which[m]))
+        ad_of = lambda m: [x for which in (lora_up, lora_dn) if m in which for x in leaves(which[m])]
+        # a stream stays in the backward while one of its adapters is trainable
+        dead = [m for m in ms if not live_in[m] and not ad_on(lora_up, m) and not ad_on(lora_dn, m) and self.prune(*of(m, "up", "down", "ln"), *ad_of(m))]
         for m in ms:
             self.live[m] = m not in dead
         b = []
@@ -311,7 +389,10 @@ class SublayerBuilders:
             du[m] = self.tmp("du%d_%d%s" % (m, par, wtag), (self.st[m].M, Im[m]))
         d1 = [self.prob(dd.get(m), self.W(names[m]["down"] + ".weight"), du.get(m), self.st[m].M, Im[m], Hm[m], Hm[m], Im[m], Im[m], R=gp[m], ldr=Im[m]) for m in ms]
         d2 = [self.prob(du.get(m), self.W(names[m]["up"] + ".weight"), dxn[m], self.st[m].M, Hm[m], Im[m], Im[m], Hm[m], Hm[m], R=dz.get(m), ldr=Hm[m]) for m in ms]
-        self.gemm_kept(b, L.NN, L.EPI_MULR, d1, [m in ma and (live_in[m] or not self.fz(*of(m, "up"))) for m in ms])
+        keep_d1 = {m: m in ma and (live_in[m] or not self.fz(*of(m, "up")) or ad_on(lora_up, m)) for m in ms}
+        self.gemm_kept(b, L.NN, L.EPI_MULR, d1, [keep_d1[m] for m in ms])
+        if lora_dn:      # directly behind d1, in front of the weight-gradient side block and d2: both read the du this op adds to, through gelu'
+            self._lora_proj_bwd(b, [(m, lora_dn[m], h[m], Tdn[m], dd[m], du[m] if keep_d1[m] else None, gp[m]) for m in ma if m in lora_dn])
         # The weight gradients need dd, h, du and x_in: everything but the LAST dgrad's output.  Their side-stream block is listed in front of that
         # dgrad, so that it starts beside a GEMM (two MFMA-bound launches share the chip without loss) instead of beside the LayerNorm backward
         # that follows, which it used to keep waiting for CUs (profiles/r03_experiments.md: 17.00 / 16.94 -> 16.52 / 16.54 ms per step).
@@ -319,6 +400,11 @@ class SublayerBuilders:
                                     lambda m: (du.get(m), x_in[m], self.G(names[m]["up"] + ".weight"), self.G(names[m]["up"] + ".bias"), Im[m], Hm[m], Im[m], Hm[m])],
                     [lambda m: of(m, "down"), lambda m: of(m, "up")], dead=dead)
         self.gemm_kept(b, L.NN, L.EPI_ADDR, d2, [m in ma and live_in[m] for m in ms])
+        if lora_up:      # behind the last dgrad: du is the gradient at the pre-activation, dxn[m] holds the base projection's input gradient
+            for m in ma:
+                if m in lora_up and not keep_d1[m]:      # no du: the adapter is frozen and nothing upstream is trainable
+                    assert self.prune(*leaves(lora_up[m]))
+            self._lora_proj_bwd(b, [(m, lora_up[m], x_in[m], Tup[m], du[m], dxn[m] if live_in[m] else None, None) for m in ma if m in lora_up and keep_d1[m]])
         return b
 
     def _wgrad(self, b, ms, shared, specs, blocks=None, dead=()):

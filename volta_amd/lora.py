@@ -1,4 +1,5 @@
-"""Low-rank adapters (LoRA) on the query / key / value projections of the encoder's attention sub-layers.
+"""Low-rank adapters (LoRA) on the linear projections of the encoder: query / key / value and the output projection of an attention
+sub-layer, the up and down projections of a feed-forward sub-layer.
 
     from volta_amd.lora import add_lora, mark_only_lora_trainable
     add_lora(model, r=8, alpha=16, targets=("query", "value"))
@@ -6,7 +7,9 @@
 
 An adapter is two ordinary parameters on the `LinearParams` holder of a projection, `lora_A` [r, in] and `lora_B` [out, r]; the engine adds
 `(alpha / r) * (x A^T) B^T` to that projection's columns of the fused Q|K|V product with the kernels of csrc/lora.hip and returns both
-parameters' gradients through the gradient arena, like any other weight's ("Low-rank adapters").  There is no LoRA
+parameters' gradients through the gradient arena, like any other weight's ("Low-rank adapters").  The targets
+`attn_out` (attention_output.dense), `ffn_up` (intermediate.dense) and `ffn_down` (output.dense) run on the vk_lora_proj_* entry points:
+the FFN-up adapter's term enters inside the GELU, the FFN-down adapter's input gradient passes through gelu'.  There is no LoRA
 dropout and one rank per model; the e4m3 projection path refuses a model with adapters."""
 import math
 
@@ -15,7 +18,10 @@ from torch import nn
 
 from .modules import LinearParams, sublayer_schedule
 
-TARGETS = ("query", "key", "value")
+TARGETS = ("query", "key", "value", "attn_out", "ffn_up", "ffn_down")
+# target -> (kind of sub-layer that hosts it, module of the sub-layer, holder name of the text stream; the vision stream's is "v_" + that)
+_PLACE = {"query": ("attn", "attention_self", "query"), "key": ("attn", "attention_self", "key"), "value": ("attn", "attention_self", "value"),
+          "attn_out": ("attn", "attention_output", "dense"), "ffn_up": ("ff", "intermediate", "dense"), "ffn_down": ("ff", "output", "dense")}
 RANKS = (4, 8, 16, 32)
 _LEAVES = (".lora_A", ".lora_B")
 
@@ -29,25 +35,28 @@ def _encoder(root):
 
 
 def _holders(root, targets=TARGETS, modalities=("text", "vision"), sublayers=None):
-    """[(holder name relative to the root, holder)] in sub-layer order, text before vision, `targets` in Q, K, V order; a holder that serves
-    both streams of a shared sub-layer is listed once."""
+    """[(holder name relative to the root, holder)] in sub-layer order; within a sub-layer Q, K, V of the text stream, then of the vision
+    stream, then the other targets of the text stream in the order of TARGETS, then those of the vision stream; a holder that serves both
+    streams of a shared sub-layer is listed once."""
     enc = _encoder(root)
     prefix = "bert.encoder." if hasattr(root, "bert") else "encoder."
     out, seen = [], set()
     for k, (n, typ) in enumerate(sublayer_schedule(root.config)):
-        if typ != "attn" or (sublayers is not None and n not in sublayers):
+        if sublayers is not None and n not in sublayers:
             continue
-        sa = enc.layer[k].attention_self
-        for mod in ("text", "vision"):
-            if mod not in modalities:
-                continue
-            for t in TARGETS:
-                name = ("v_" if mod == "vision" else "") + t
-                holder = sa._modules.get(name)
-                if t in targets and isinstance(holder, LinearParams) and id(holder) not in seen:
-                    seen.add(id(holder))
-                    alias = t if sa._modules.get(t) is holder else name          # a shared sub-layer's v_query IS query: its first name
-                    out.append(("%slayer.%d.attention_self.%s" % (prefix, k, alias), holder))
+        for group in (TARGETS[:3], TARGETS[3:]):
+            for mod in ("text", "vision"):
+                for t in group:
+                    kind, module, base = _PLACE[t]
+                    if kind != typ or t not in targets or mod not in modalities:
+                        continue
+                    node = enc.layer[k]._modules[module]
+                    name = ("v_" if mod == "vision" else "") + base
+                    holder = node._modules.get(name)
+                    if isinstance(holder, LinearParams) and id(holder) not in seen:
+                        seen.add(id(holder))
+                        alias = base if node._modules.get(base) is holder else name          # a shared sub-layer's v_query IS query: its first name
+                        out.append(("%slayer.%d.%s.%s" % (prefix, k, module, alias), holder))
     return out
 
 
@@ -70,11 +79,12 @@ def add_lora(model, r=8, alpha=16, targets=("query", "value"), modalities=("text
         raise ValueError("LoRA alpha %r must be positive" % (alpha,))
     if getattr(root, "lora_config", None) is not None or _adapted(root):
         raise RuntimeError("the model already has LoRA adapters (one rank and scale per model): merge_lora() or remove_lora() first")
-    attn = [n for n, typ in sublayer_schedule(root.config) if typ == "attn"]
+    kinds = {_PLACE[t][0] for t in targets}
+    hosts = [n for n, typ in sublayer_schedule(root.config) if typ in kinds]          # the sub-layers that host one of the chosen targets
     if sublayers is not None:
         sublayers = sorted(int(n) for n in sublayers)
-        if not sublayers or any(n not in attn for n in sublayers):
-            raise ValueError("LoRA sublayers %r: attention sub-layers of this config are %s" % (sublayers, attn))
+        if not sublayers or any(n not in hosts for n in sublayers):
+            raise ValueError("LoRA sublayers %r: the sub-layers of this config that host one of %r are %s" % (sublayers, targets, hosts))
     holders = _holders(root, targets, modalities, sublayers)
     if not holders:
         raise ValueError("no projection matches targets %r, modalities %r, sublayers %r" % (targets, modalities, sublayers))
@@ -90,7 +100,7 @@ def add_lora(model, r=8, alpha=16, targets=("query", "value"), modalities=("text
             getattr(h, leaf)._vk_owner = root
             names.append("%s.%s" % (name, leaf))
     root.lora_config = dict(r=int(r), alpha=float(alpha), targets=list(targets), modalities=list(modalities),
-                            sublayers=list(attn if sublayers is None else sublayers))
+                            sublayers=list(hosts if sublayers is None else sublayers))
     root._invalidate_engine()
     return names
 

@@ -516,3 +516,71 @@ def lora_bwd(problems, work=None):
     assert work.numel() * work.element_size() >= need and work.data_ptr() % 16 == 0
     check(L.lib.vk_lora_bwd(arr, len(problems), ptr(work), stream_ptr()))
     return work
+
+
+# ---- adapters on a whole projection (vk_lora_proj_*): K and N up to 4096, the GELU in the forward, a saved gelu' in the input gradient
+def _lora_proj_common(X, A, B, T, Y, M, what):
+    r, K = A.shape
+    N = B.shape[0]
+    assert r in (4, 8, 16, 32) and tuple(B.shape) == (N, r), "A [r, K] and B [N, r] with r in 4, 8, 16, 32"
+    assert K % 64 == 0 and N % 64 == 0 and K <= 4096 and N <= 4096, "K and N: multiples of 64, at most 4096"
+    for t in (X, A, B, T, Y):
+        _bf16(t)
+        assert t.data_ptr() % 16 == 0, "16-byte alignment required"
+    assert A.is_contiguous() and B.is_contiguous() and T.is_contiguous(), "A, B and T are dense"
+    ldx, ldy = X.stride(0), Y.stride(0)
+    assert X.stride(1) == 1 and Y.stride(1) == 1 and ldx % 8 == 0 and ldy % 8 == 0 and ldx >= K and ldy >= N
+    assert X.shape[1] == K and Y.shape[1] == N, "%s: X [M, K] and Y [M, N]" % what
+    assert M <= X.shape[0] and M <= Y.shape[0] and (M == 0 or ((M - 1) * ldx + K <= _extent(X) and (M - 1) * ldy + N <= _extent(Y)))
+    assert T.numel() >= M * r
+    return r, K, N, ldx, ldy
+
+
+def _lora_side(t, M, cols, what):
+    """A bf16 [M, cols] operand beside X or Y (G, R, dX) -> its leading dimension."""
+    _bf16(t)
+    ld = t.stride(0)
+    assert t.stride(1) == 1 and t.shape[1] == cols and ld % 8 == 0 and ld >= cols and t.data_ptr() % 16 == 0, what
+    assert M <= t.shape[0] and (M == 0 or (M - 1) * ld + cols <= _extent(t)), what
+    return ld
+
+
+def lora_proj_problem(X, A, B, T, Y, scale, G=None, M=None, dyn=None):
+    """One vk_lora_proj_problem.  G None: Y += s (X A^T) B^T; G [M, N]: Y = gelu(Y + ...), G = gelu'(Y + ...)."""
+    M = X.shape[0] if M is None else M
+    r, K, N, ldx, ldy = _lora_proj_common(X, A, B, T, Y, M, "lora_proj_problem")
+    ldg = 0 if G is None else _lora_side(G, M, N, "G")
+    return L.LoraProjProblem(ptr(X), ptr(A), ptr(B), ptr(T), ptr(Y), ptr(G), ptr(dyn), M, K, N, r, ldx, ldy, ldg, float(scale), int(G is not None))
+
+
+def lora_proj_bwd_problem(X, A, B, T, dY, dT, dX, dA, dB, scale, R=None, M=None, accumulate=False, dyn=None):
+    """One vk_lora_proj_bwd_problem; dX None: the input gradient is not live; dA and dB None: a frozen adapter; R: the gelu' buffer of the
+    GEMM that produced X, multiplied into the adapter's share of dX."""
+    M = X.shape[0] if M is None else M
+    r, K, N, ldx, ldy = _lora_proj_common(X, A, B, T, dY, M, "lora_proj_bwd_problem")
+    _bf16(dT)
+    assert dT.is_contiguous() and dT.numel() >= M * r and dT.data_ptr() % 16 == 0
+    assert (dA is None) == (dB is None), "dA and dB: both or neither"
+    if dA is not None:
+        for g, shape in ((dA, (r, K)), (dB, (N, r))):
+            assert g.dtype == torch.float32 and g.is_cuda and g.is_contiguous() and tuple(g.shape) == shape and g.data_ptr() % 16 == 0
+    lddx = 0 if dX is None else _lora_side(dX, M, K, "dX")
+    ldr = 0 if R is None else _lora_side(R, M, K, "R")
+    return L.LoraProjBwdProblem(ptr(X), ptr(A), ptr(B), ptr(T), ptr(dY), ptr(dT), ptr(dX), ptr(dA), ptr(dB), ptr(R), ptr(dyn), M, K, N, r, ldx, ldy,
+                                lddx, ldr, int(bool(accumulate)), float(scale))
+
+
+def lora_proj_fwd(problems):
+    arr = (L.LoraProjProblem * len(problems))(*problems)
+    check(L.lib.vk_lora_proj_fwd(arr, len(problems), stream_ptr()))
+
+
+def lora_proj_bwd(problems, work=None):
+    arr = (L.LoraProjBwdProblem * len(problems))(*problems)
+    need = L.lib.vk_lora_proj_bwd_work_bytes(arr, len(problems))
+    assert need > 0, "vk_lora_proj_bwd_work_bytes refused the problems"
+    if work is None:
+        work = torch.empty(need, dtype=torch.uint8, device="cuda")
+    assert work.numel() * work.element_size() >= need and work.data_ptr() % 16 == 0
+    check(L.lib.vk_lora_proj_bwd(arr, len(problems), ptr(work), stream_ptr()))
+    return work
