@@ -751,6 +751,29 @@ int vk_lora_proj_bwd(const vk_lora_proj_bwd_problem* p, int n, void* work, vk_st
 /* Bytes of `work` for these problems (reads M, K, N, r only); negative on bad arguments. */
 int64_t vk_lora_proj_bwd_work_bytes(const vk_lora_proj_bwd_problem* p, int n);
 
+/* ------------------------------------------------------------------------------------------------
+ * LoRA dropout: the four entry points above with a keep mask on the adapter's input X (and on X only: the base projection reads the
+ * unmasked X).  `drop` is a parallel array, one vk_dropout per problem, read on the host.  It follows the dropout contract at the top
+ * of this header: element (m, k) of the problem's X [M, K] -- m is the row inside X as passed -- takes word k & 3 of
+ * Philox-4x32-7(counter = (k >> 2, m, drop[i].site, 0), key = *drop[i].seed) and is kept, keep[m,k] = 1, when the word is >=
+ * drop[i].threshold; c = drop[i].scale = 1 / (1 - p).  No mask is stored: the backward replays the stream, so a problem's backward
+ * entry names the site, seed and threshold of its forward entry.  Each problem (one adapter on one stream) has a site of its own.
+ * Rounding points, where they differ from the unmasked entry points':
+ *   forward    T   = bf16(c * sum_k keep[m,k] X[m,k] A[j,k])             fp32 accumulation, ONE multiply by c after the sum
+ *              Y   as above: it reads the bf16 T it stored (act = 1 / G unchanged)
+ *   backward   dT, dB as above (T already carries the mask)
+ *              dA  = c * sum_m keep[m,k] dT[m,j] X[m,k]                   c multiplies a problem's finished sum over m, before that sum
+ *                                                                        joins another problem's (a shared adapter) or the `accumulate` value
+ *              dX  = bf16(float(dX) + rho[m,k] * sum_c keep_c[m,k] * c_c * sum_j dT_c[m,j] A_c[j,k])      rho = R or 1, as above
+ * dA / dB stay deterministic (the same fixed row blocks, summed in index order); a frozen adapter (dA == dB == NULL) with a dX still
+ * masks its share of dX.  A problem with threshold 0 is not masked and its seed is not read: it produces the bits of the unmasked
+ * entry point (with every threshold 0 the call runs the unmasked kernels).  Refusals as above, made on the host before any launch,
+ * plus: a NULL `drop`, a threshold != 0 with a NULL or misaligned (8 bytes) seed, a threshold != 0 with a scale that is not > 0. */
+int vk_lora_fwd_drop(const vk_lora_problem* p, const vk_dropout* drop, int n, vk_stream_t s);
+int vk_lora_bwd_drop(const vk_lora_bwd_problem* p, const vk_dropout* drop, int n, void* work, vk_stream_t s);
+int vk_lora_proj_fwd_drop(const vk_lora_proj_problem* p, const vk_dropout* drop, int n, vk_stream_t s);
+int vk_lora_proj_bwd_drop(const vk_lora_proj_bwd_problem* p, const vk_dropout* drop, int n, void* work, vk_stream_t s);
+
 /* out[i] = a[i] * b[i] (bf16); processes rows * row_len elements where rows = min(*dyn_rows, n / row_len)
  * when dyn_rows != NULL.  (d gelu(u) = dz * gelu'(u) in the prediction-head transforms.)  n and row_len multiples of 8; a, b and
  * out 16-byte aligned (refused otherwise). */
@@ -799,7 +822,11 @@ enum {
     VK_FN_LORA_FWD,      /* vk_lora_fwd(p[0], n[0]) */
     VK_FN_LORA_BWD,      /* vk_lora_bwd(p[0], n[0], p[1]) */
     VK_FN_LORA_PROJ_FWD, /* vk_lora_proj_fwd(p[0], n[0]) */
-    VK_FN_LORA_PROJ_BWD  /* vk_lora_proj_bwd(p[0], n[0], p[1]) */
+    VK_FN_LORA_PROJ_BWD, /* vk_lora_proj_bwd(p[0], n[0], p[1]) */
+    VK_FN_LORA_FWD_DROP, /* vk_lora_fwd_drop(p[0], p[2], n[0]): p[2] = vk_dropout[n[0]] */
+    VK_FN_LORA_BWD_DROP, /* vk_lora_bwd_drop(p[0], p[2], n[0], p[1]) */
+    VK_FN_LORA_PROJ_FWD_DROP, /* vk_lora_proj_fwd_drop(p[0], p[2], n[0]) */
+    VK_FN_LORA_PROJ_BWD_DROP  /* vk_lora_proj_bwd_drop(p[0], p[2], n[0], p[1]) */
 };                       /* VK_FN_POOL_FWD / VK_FN_POOL_BWD: n[3] = fusion mode (VK_FUSE_*) */
 typedef struct vk_generic_args {   /* positional arguments of the small entry points, see executor.cpp */
     int32_t fn;

@@ -3,12 +3,13 @@
   python tools/bench_lora.py [--steps 20] [--out profiles/lora.md]
 
 The VQA-shaped step of tools/bench_task_step.py (ctrl_vilbert_base, B = 256, T = 23, 36 + 1 regions, 3129 labels; forward, fused task loss,
-backward, clip, AdamW over the trainable parameters) in five variants:
+backward, clip, AdamW over the trainable parameters) in six variants:
   full      every parameter trains
   head      the encoder frozen, only the task head trains
   lora8     LoRA r = 8 on query and value + the head
   lora16    LoRA r = 16 on query, key and value + the head
   lora8_all LoRA r = 8 on all six targets (query, key, value, attn_out, ffn_up, ffn_down), both streams + the head
+  lora8_drop lora8 with LoRA dropout 0.1: the masked kernels (vk_lora_fwd_drop / vk_lora_bwd_drop)
 The variants alternate step by step after a warm-up of all of them; every step is timed between device synchronisations and the report gives
 the median of `steps` steps per variant, as tools/bench_backbone.py does.  A second pass runs both lists of each LoRA variant through
 vk_run_ops_timed and reports the time per LoRA launch (the Q|K|V ops and the whole-projection ops of attn_out / ffn_up / ffn_down) against the bytes the launch moves at the 6.3 TB/s copy rate of VERDICT.md item 10.
@@ -26,7 +27,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
-VARIANTS = ("full", "head", "lora8", "lora16", "lora8_all")
+VARIANTS = ("full", "head", "lora8", "lora16", "lora8_all", "lora8_drop")
 COPY_RATE = 6.3e12
 
 
@@ -41,6 +42,8 @@ def make(variant):
         lora.add_lora(model, r=16, alpha=32, targets=("query", "key", "value"))
     elif variant == "lora8_all":
         lora.add_lora(model, r=8, alpha=16, targets=lora.TARGETS)
+    elif variant == "lora8_drop":
+        lora.add_lora(model, r=8, alpha=16, targets=("query", "value"), dropout=0.1)
     if variant.startswith("lora"):
         lora.mark_only_lora_trainable(model, also=("clfs_dict.",))
     elif variant == "head":
@@ -142,13 +145,15 @@ def main():
     lines += ["", "lora8 - full = %+.3f ms (%+.1f %%); lora8 - head = %+.3f ms; lora16 - lora8 = %+.3f ms" %
               (med["lora8"] - med["full"], 100 * (med["lora8"] - med["full"]) / med["full"], med["lora8"] - med["head"], med["lora16"] - med["lora8"]),
               "lora8_all - full = %+.3f ms (%+.1f %%); lora8_all - head = %+.3f ms; lora8_all - lora8 = %+.3f ms" %
-              (med["lora8_all"] - med["full"], 100 * (med["lora8_all"] - med["full"]) / med["full"], med["lora8_all"] - med["head"], med["lora8_all"] - med["lora8"]), "",
+              (med["lora8_all"] - med["full"], 100 * (med["lora8_all"] - med["full"]) / med["full"], med["lora8_all"] - med["head"], med["lora8_all"] - med["lora8"]),
+              "lora8_drop - lora8 = %+.3f ms (%+.1f %%)" % (med["lora8_drop"] - med["lora8"], 100 * (med["lora8_drop"] - med["lora8"]) / med["lora8"]), "",
               "## LoRA launches", "", "Per-op times from vk_run_ops_timed (side-stream blocks inline), averaged over %d steps; bytes: what a launch reads and writes;" % args.steps,
               "floor: those bytes at the 6.3 TB/s streaming-copy rate of VERDICT.md item 10.", "",
               "| variant | list | LoRA ops | ms per op | MB per op | floor, ms | time / floor | LoRA share of the list |", "|---|---|---|---|---|---|---|---|"]
     from volta_amd import _lib as L
     for v, fns, count, tag in (("lora8", None, lora_bytes, ""), ("lora16", None, lora_bytes, ""), ("lora8_all", None, lora_bytes, " (Q|K|V ops)"),
-                               ("lora8_all", (L.FN_LORA_PROJ_FWD, L.FN_LORA_PROJ_BWD), lora_proj_bytes, " (whole-projection ops)")):
+                               ("lora8_all", (L.FN_LORA_PROJ_FWD, L.FN_LORA_PROJ_BWD), lora_proj_bytes, " (whole-projection ops)"),
+                               ("lora8_drop", (L.FN_LORA_FWD_DROP, L.FN_LORA_BWD_DROP), lora_bytes, " (masked)")):
         res, eng = launch_times(states[v], args.steps, fns)
         nbytes = count(eng)
         for (ms, n, total), b, name in zip(res, nbytes, ("forward", "backward")):

@@ -248,7 +248,7 @@ class Op(C.Structure):
  FN_LOSS_FINAL, FN_POOL_FWD, FN_POOL_BWD, FN_MASK_PREP, FN_MUL, FN_VLBERT_PREP, FN_VLBERT_MASKGRAD, FN_ROWGROUP_SUM,
  FN_RELU_BWD, FN_COPY, FN_SUM_SLABS, FN_SUM_SLABS_BF16, FN_SIDE_TAIL, FN_QUANT_ROWS, FN_CAST_FP8, FN_VIS_LOSS_FWD, FN_VIS_LOSS_BWD,
  FN_NCE_NEG, FN_TEXT_END_ROWS, FN_VLBERT_OBJ_IDS, FN_VLBERT_POSITIONS, FN_HOLD, FN_GATE, FN_BUMP, FN_GRAD_SEED, FN_LORA_FWD, FN_LORA_BWD,
- FN_LORA_PROJ_FWD, FN_LORA_PROJ_BWD) = range(1, 39)
+ FN_LORA_PROJ_FWD, FN_LORA_PROJ_BWD, FN_LORA_FWD_DROP, FN_LORA_BWD_DROP, FN_LORA_PROJ_FWD_DROP, FN_LORA_PROJ_BWD_DROP) = range(1, 43)
 
 
 class AttnArgs(C.Structure):
@@ -383,6 +383,10 @@ _sig("vk_lora_bwd_work_bytes", C.c_int64, C.POINTER(LoraBwdProblem), C.c_int)
 _sig("vk_lora_proj_fwd", C.c_int, C.POINTER(LoraProjProblem), C.c_int, c_p)
 _sig("vk_lora_proj_bwd", C.c_int, C.POINTER(LoraProjBwdProblem), C.c_int, c_p, c_p)
 _sig("vk_lora_proj_bwd_work_bytes", C.c_int64, C.POINTER(LoraProjBwdProblem), C.c_int)
+_sig("vk_lora_fwd_drop", C.c_int, C.POINTER(LoraProblem), C.POINTER(Dropout), C.c_int, c_p)
+_sig("vk_lora_bwd_drop", C.c_int, C.POINTER(LoraBwdProblem), C.POINTER(Dropout), C.c_int, c_p, c_p)
+_sig("vk_lora_proj_fwd_drop", C.c_int, C.POINTER(LoraProjProblem), C.POINTER(Dropout), C.c_int, c_p)
+_sig("vk_lora_proj_bwd_drop", C.c_int, C.POINTER(LoraProjBwdProblem), C.POINTER(Dropout), C.c_int, c_p, c_p)
 _sig("vk_run_ops", C.c_int, C.POINTER(Op), C.c_int, c_p)
 _sig("vk_run_ops_timed", C.c_int, C.POINTER(Op), C.c_int, c_p, C.POINTER(C.c_float))
 _sig("vk_ln_bwd_finalize", C.c_int, C.POINTER(LnBwdArgs), c_p)
@@ -406,6 +410,7 @@ EXPORTS = ["vk_version", "vk_device_arch", "vk_last_error", "vk_set_seed", "vk_c
            "vk_lmdb_open", "vk_lmdb_close", "vk_lmdb_entries", "vk_lmdb_first", "vk_lmdb_next", "vk_lmdb_get", "vk_concap_record_decode", "vk_concap_records_decode", "vk_b64_decode",
            "vk_wordpiece_open", "vk_wordpiece_close", "vk_wordpiece_vocab_size", "vk_wordpiece_token_id", "vk_wordpiece_encode", "vk_wordpiece_encode_batch",
            "vk_lora_fwd", "vk_lora_bwd", "vk_lora_bwd_work_bytes", "vk_lora_proj_fwd", "vk_lora_proj_bwd", "vk_lora_proj_bwd_work_bytes",
+           "vk_lora_fwd_drop", "vk_lora_bwd_drop", "vk_lora_proj_fwd_drop", "vk_lora_proj_bwd_drop",
            "vk_task_batch", "vk_task_images_stage", "vk_retrieval_ranks", "vk_retrieval_ranks_shard_rows", "vk_retrieval_ranks_shard_cols", "vk_retrieval_ranks_finish", "vk_image_means", "vk_knn_pool_work_bytes", "vk_knn_pool"]
 
 

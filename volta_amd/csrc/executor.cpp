@@ -207,6 +207,16 @@ static int run_one(const vk_op& o, int i, vk_stream_t s) {
                     case VK_FN_LORA_BWD: rc = vk_lora_bwd((const vk_lora_bwd_problem*)g->p[0], (int)g->n[0], g->p[1], s); break;
                     case VK_FN_LORA_PROJ_FWD: rc = vk_lora_proj_fwd((const vk_lora_proj_problem*)g->p[0], (int)g->n[0], s); break;
                     case VK_FN_LORA_PROJ_BWD: rc = vk_lora_proj_bwd((const vk_lora_proj_bwd_problem*)g->p[0], (int)g->n[0], g->p[1], s); break;
+                    case VK_FN_LORA_FWD_DROP: rc = vk_lora_fwd_drop((const vk_lora_problem*)g->p[0], (const vk_dropout*)g->p[2], (int)g->n[0], s); break;
+                    case VK_FN_LORA_BWD_DROP:
+                        rc = vk_lora_bwd_drop((const vk_lora_bwd_problem*)g->p[0], (const vk_dropout*)g->p[2], (int)g->n[0], g->p[1], s);
+                        break;
+                    case VK_FN_LORA_PROJ_FWD_DROP:
+                        rc = vk_lora_proj_fwd_drop((const vk_lora_proj_problem*)g->p[0], (const vk_dropout*)g->p[2], (int)g->n[0], s);
+                        break;
+                    case VK_FN_LORA_PROJ_BWD_DROP:
+                        rc = vk_lora_proj_bwd_drop((const vk_lora_proj_bwd_problem*)g->p[0], (const vk_dropout*)g->p[2], (int)g->n[0], g->p[1], s);
+                        break;
                     case VK_FN_SUM_SLABS: rc = vk_sum_slabs_f32((float*)g->p[0], (const float*)g->p[1], g->n[0], (int)g->n[1], g->n[2], s); break;
                     default: rc = vk::set_error("vk_run_ops: unknown generic fn %d at op %d", g->fn, i);
                 }

@@ -12,6 +12,9 @@
 //                                                   reduce      the blocks summed in index order (no float atomics: same bits every run)
 //             dxn = bf16(dxn + sum_c dT_c A_c)      expand      every adapter of a stream in ONE read-modify-write of dxn
 // Two launches forward, four backward, each over all (<= 6) problems of the call.
+// LoRA dropout (vk_lora_*_drop): the same launches with a Philox keep mask on the adapter's input X where it is read -- the rowdot of T,
+// the colpartial of dA, the expand of dX -- and 1 / (1 - p) where a scale was 1 (rowdot's, reduce's member, expand's member).  The
+// unmasked kernels are untouched instantiations: see keep_mask8.
 #include "common.h"
 #include "../../include/volta_hip.h"
 #include "util.h"
@@ -84,10 +87,28 @@ __device__ __forceinline__ float dot2(uint32_t a, uint32_t b, float c) {       /
     return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16pair, a), __builtin_bit_cast(bf16pair, b), c, false);
 }
 
+// ---- LoRA dropout (vk_lora_*_drop): the keep decisions of the 8 elements (row, k .. k + 7), k a multiple of 8, of the site `d` -- two
+// Philox calls -- as a mask on the packed bf16 pairs of a 16-byte load: 0xFFFF over a kept element's half, 0 over a dropped one's.
+// A masked kernel is the instantiation with one more argument (the sites of its jobs) of the kernel the unmasked entry points launch:
+// kernel<R> is the code it was without the mask, kernel<R, RowdotDrop> the masked form.
+__device__ __forceinline__ u32x4 keep_mask8(const DropCfg& d, uint64_t seed, uint32_t row, uint32_t k) {
+    const u32x4 w0 = drop_words(d, seed, row, k >> 2), w1 = drop_words(d, seed, row, (k >> 2) + 1);
+    u32x4 m;
+    m[0] = (w0[0] >= d.thr ? 0xFFFFu : 0u) | (w0[1] >= d.thr ? 0xFFFF0000u : 0u);
+    m[1] = (w0[2] >= d.thr ? 0xFFFFu : 0u) | (w0[3] >= d.thr ? 0xFFFF0000u : 0u);
+    m[2] = (w1[0] >= d.thr ? 0xFFFFu : 0u) | (w1[1] >= d.thr ? 0xFFFF0000u : 0u);
+    m[3] = (w1[2] >= d.thr ? 0xFFFFu : 0u) | (w1[3] >= d.thr ? 0xFFFF0000u : 0u);
+    return m;
+}
+struct RowdotDrop { DropCfg d[LORA_MAXP]; };                 // per job; thr = 0: the job is not masked (seed is not read)
+template <typename T> __device__ __forceinline__ const T& the_drop(const T& d) { return d; }
+
 // A wave takes 4 rows at a time: a lane holds 8 elements of each row, reads the panel's 8 elements per j from LDS once for the four rows
-// and feeds packed bf16 pairs to v_dot2c_f32_bf16 (no unpacking); the 4 R lane sums are then combined across the wave.
-template <int R>
-__global__ __launch_bounds__(256) void lora_rowdot_kernel(const RowdotArgs a) {
+// and feeds packed bf16 pairs to v_dot2c_f32_bf16 (no unpacking); the 4 R lane sums are then combined across the wave.  DROP: P is the
+// adapter's input, its packed pairs are ANDed with the keep mask in front of the dots (1 / (1 - p) is the job's `scale`).
+template <int R, typename... D>
+__global__ __launch_bounds__(256) void lora_rowdot_kernel(const RowdotArgs a, const D... d) {
+    constexpr bool DROP = sizeof...(D) == 1;
     constexpr int RW = 4, V = RW * R, OWN = V / 64 > 1 ? V / 64 : 1;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     uint16_t* Qs = (uint16_t*)smem;                  // [R][Kc]
@@ -97,6 +118,12 @@ __global__ __launch_bounds__(256) void lora_rowdot_kernel(const RowdotArgs a) {
     const int Kc = jb.Kc, rows = rows_of(jb.M, jb.dyn);
     const int row0 = ((int)blockIdx.x - a.start[p]) * ROWDOT_ROWS;
     if (row0 >= rows) return;
+    DropCfg dc = {};
+    uint64_t seed = 0;
+    if constexpr (DROP) {
+        dc = the_drop(d...).d[p];
+        if (dc.thr) seed = *dc.seed;
+    }
     for (int i = threadIdx.x; i < R * Kc; i += 256) {
         const int j = i / Kc, k = i - j * Kc;
         Qs[i] = jb.Q[(size_t)j * jb.qs_j + (size_t)k * jb.qs_k];
@@ -115,6 +142,12 @@ __global__ __launch_bounds__(256) void lora_rowdot_kernel(const RowdotArgs a) {
             u32x4 x[RW];
 #pragma unroll
             for (int i = 0; i < RW; ++i) x[i] = *(const u32x4*)(prow[i] + k0);
+            if constexpr (DROP) {
+                if (dc.thr) {
+#pragma unroll
+                    for (int i = 0; i < RW; ++i) x[i] &= keep_mask8(dc, seed, uniform32((uint32_t)(m0 + i)), (uint32_t)k0);
+                }
+            }
 #pragma unroll
             for (int j = 0; j < R; ++j) {
                 const u32x4 q = *(const u32x4*)(Qs + j * Kc + k0);
@@ -146,8 +179,13 @@ struct ExpandJob {
 };
 struct ExpandArgs { ExpandJob job[LORA_MAXP]; int start[LORA_MAXP + 1]; int n; };
 
-template <int R>
-__global__ __launch_bounds__(256) void lora_expand_kernel(const ExpandArgs a) {
+struct ExpandDrop { DropCfg d[LORA_MAXP][3]; };              // per job and member; thr = 0: the member is not masked
+
+// DROP (the input gradient): member c's sum over j is zeroed where its site dropped element (m, x) of the input; 1 / (1 - p) is the
+// member's `scale`.
+template <int R, typename... D>
+__global__ __launch_bounds__(256) void lora_expand_kernel(const ExpandArgs a, const D... d) {
+    constexpr bool DROP = sizeof...(D) == 1;
     constexpr int JC = R < 8 ? R : 8;
     int p = 0;
     while (p + 1 < a.n && (int)blockIdx.x >= a.start[p + 1]) ++p;
@@ -196,6 +234,21 @@ __global__ __launch_bounds__(256) void lora_expand_kernel(const ExpandArgs a) {
                 }
             }
         }
+        if constexpr (DROP) {
+            const DropCfg dc = the_drop(d...).d[p][c];
+            if (dc.thr) {
+                const uint64_t seed = *dc.seed;
+#pragma unroll
+                for (int i = 0; i < EXPAND_RPT; ++i) {
+                    if (i < nr) {
+                        const u32x4 km = keep_mask8(dc, seed, (uint32_t)(m0 + i), (uint32_t)x);
+#pragma unroll
+                        for (int e = 0; e < 8; ++e)
+                            if (!(km[e >> 1] & (e & 1 ? 0x10000u : 1u))) part[i][e] = 0.f;
+                    }
+                }
+            }
+        }
 #pragma unroll
         for (int i = 0; i < EXPAND_RPT; ++i)
 #pragma unroll
@@ -223,8 +276,12 @@ struct ColpJob {
 };
 struct ColpArgs { ColpJob job[2 * LORA_MAXP]; int start[2 * LORA_MAXP + 1]; int n; };
 
-template <int R>
-__global__ __launch_bounds__(256) void lora_colpartial_kernel(const ColpArgs a) {
+struct ColpDrop { DropCfg d[2 * LORA_MAXP]; };               // per job; thr = 0 (every dB job: T carries the mask already): not masked
+
+// DROP (a dA job): P is the adapter's input, masked like the forward's; 1 / (1 - p) is applied by reduce.
+template <int R, typename... D>
+__global__ __launch_bounds__(256) void lora_colpartial_kernel(const ColpArgs a, const D... d) {
+    constexpr bool DROP = sizeof...(D) == 1;
     constexpr int JG = R / 4, TPS = 8 * JG, NS = 256 / TPS;
     __shared__ float red[256 * 33];                 // [lane][32 (+1: the slices of one output sit 32 * TPS words apart)]
     int p = 0;
@@ -238,6 +295,12 @@ __global__ __launch_bounds__(256) void lora_colpartial_kernel(const ColpArgs a) 
     const int chunk = t & 7, jg = t >> 3;
     const int x0 = tile * COLP_COLS + chunk * 8;
     const int row_lo = blk * LORA_RB, row_hi = row_lo + LORA_RB < rows ? row_lo + LORA_RB : rows;
+    DropCfg dc = {};
+    uint64_t seed = 0;
+    if constexpr (DROP) {
+        dc = the_drop(d...).d[p];
+        if (dc.thr) seed = *dc.seed;
+    }
     float acc[4][8];
 #pragma unroll
     for (int jj = 0; jj < 4; ++jj)
@@ -245,7 +308,11 @@ __global__ __launch_bounds__(256) void lora_colpartial_kernel(const ColpArgs a) 
         for (int e = 0; e < 8; ++e) acc[jj][e] = 0.f;
     for (int m = row_lo + slice; m < row_hi; m += NS) {
         float x[8], tv[4];
-        unpack8(*(const u32x4*)(jb.P + (size_t)m * jb.ldp + x0), x);
+        u32x4 xp = *(const u32x4*)(jb.P + (size_t)m * jb.ldp + x0);
+        if constexpr (DROP) {
+            if (dc.thr) xp &= keep_mask8(dc, seed, (uint32_t)m, (uint32_t)x0);
+        }
+        unpack8(xp, x);
         load_bf<4>(jb.T + (size_t)m * R + jg * 4, tv);
 #pragma unroll
         for (int jj = 0; jj < 4; ++jj)
@@ -311,17 +378,37 @@ int check_common(const char* fn, int i, int M, int K, int N, int r, int ldx, int
 int nblk_of(int M) { return M > 0 ? (M + VK_LORA_ROW_BLOCK - 1) / VK_LORA_ROW_BLOCK : 0; }
 int64_t round256(int64_t v) { return (v + 255) & ~(int64_t)255; }
 
-template <typename Args, typename K4, typename K8, typename K16, typename K32>
-void launch_by_r(int r, K4 k4, K8 k8, K16 k16, K32 k32, int blocks, size_t lds, hipStream_t st, const Args& a) {
+template <typename K4, typename K8, typename K16, typename K32, typename... Args>
+void launch_by_r(int r, K4 k4, K8 k8, K16 k16, K32 k32, int blocks, size_t lds, hipStream_t st, const Args&... a) {
     switch (r) {
-        case 4: hipLaunchKernelGGL(k4, dim3(blocks), dim3(256), lds, st, a); break;
-        case 8: hipLaunchKernelGGL(k8, dim3(blocks), dim3(256), lds, st, a); break;
-        case 16: hipLaunchKernelGGL(k16, dim3(blocks), dim3(256), lds, st, a); break;
-        default: hipLaunchKernelGGL(k32, dim3(blocks), dim3(256), lds, st, a);
+        case 4: hipLaunchKernelGGL(k4, dim3(blocks), dim3(256), lds, st, a...); break;
+        case 8: hipLaunchKernelGGL(k8, dim3(blocks), dim3(256), lds, st, a...); break;
+        case 16: hipLaunchKernelGGL(k16, dim3(blocks), dim3(256), lds, st, a...); break;
+        default: hipLaunchKernelGGL(k32, dim3(blocks), dim3(256), lds, st, a...);
     }
 }
 
-int launch_rowdot(const char* fn, int r, vk::RowdotArgs& a, int maxK, hipStream_t st) {
+// LoRA dropout: entry i of a _drop call's vk_dropout array as the kernels take it; threshold 0 = not masked, scale 1
+vk::DropCfg drop_cfg(const vk_dropout* drop, int i) {
+    if (!drop || !drop[i].threshold) return vk::DropCfg{nullptr, 0u, 0u, 1.0f};
+    return vk::DropCfg{drop[i].seed, drop[i].site, drop[i].threshold, drop[i].scale};
+}
+int check_drop(const char* fn, const vk_dropout* drop, int n) {
+    if (!drop) return vk::set_error("%s: NULL dropout array (one vk_dropout per problem)", fn);
+    for (int i = 0; i < n; ++i) {
+        if (drop[i].threshold && !drop[i].seed) return vk::set_error("%s: problem %d: threshold %u with a NULL seed", fn, i, drop[i].threshold);
+        if (drop[i].threshold && ((uintptr_t)drop[i].seed & 7)) return vk::set_error("%s: problem %d: the seed is not 8-byte aligned", fn, i);
+        if (drop[i].threshold && !(drop[i].scale > 0.f)) return vk::set_error("%s: problem %d: scale %g (1 / (1 - p))", fn, i, (double)drop[i].scale);
+    }
+    return 0;
+}
+bool any_drop(const vk_dropout* drop, int n) {
+    for (int i = 0; drop && i < n; ++i)
+        if (drop[i].threshold) return true;
+    return false;
+}
+
+int launch_rowdot(const char* fn, int r, vk::RowdotArgs& a, int maxK, hipStream_t st, const vk::RowdotDrop* d = nullptr) {
     int blocks = 0;
     for (int i = 0; i < a.n; ++i) { a.start[i] = blocks; blocks += (a.job[i].M + vk::ROWDOT_ROWS - 1) / vk::ROWDOT_ROWS; }
     a.start[a.n] = blocks;
@@ -332,12 +419,23 @@ int launch_rowdot(const char* fn, int r, vk::RowdotArgs& a, int maxK, hipStream_
         hipFuncSetAttribute((const void*)vk::lora_rowdot_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, 16 * 1024 * 2),
         hipFuncSetAttribute((const void*)vk::lora_rowdot_kernel<32>, hipFuncAttributeMaxDynamicSharedMemorySize, 32 * 1024 * 2)};
     (void)attr;
+    if (d) {
+        static const hipError_t attr_d[4] = {
+            hipFuncSetAttribute((const void*)vk::lora_rowdot_kernel<4, vk::RowdotDrop>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 1024 * 2),
+            hipFuncSetAttribute((const void*)vk::lora_rowdot_kernel<8, vk::RowdotDrop>, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * 1024 * 2),
+            hipFuncSetAttribute((const void*)vk::lora_rowdot_kernel<16, vk::RowdotDrop>, hipFuncAttributeMaxDynamicSharedMemorySize, 16 * 1024 * 2),
+            hipFuncSetAttribute((const void*)vk::lora_rowdot_kernel<32, vk::RowdotDrop>, hipFuncAttributeMaxDynamicSharedMemorySize, 32 * 1024 * 2)};
+        (void)attr_d;
+        launch_by_r(r, vk::lora_rowdot_kernel<4, vk::RowdotDrop>, vk::lora_rowdot_kernel<8, vk::RowdotDrop>, vk::lora_rowdot_kernel<16, vk::RowdotDrop>, vk::lora_rowdot_kernel<32, vk::RowdotDrop>,
+                    blocks, (size_t)r * maxK * 2, st, a, *d);
+        return vk::check_launch(fn);
+    }
     launch_by_r(r, vk::lora_rowdot_kernel<4>, vk::lora_rowdot_kernel<8>, vk::lora_rowdot_kernel<16>, vk::lora_rowdot_kernel<32>, blocks,
                 (size_t)r * maxK * 2, st, a);
     return vk::check_launch(fn);
 }
 
-int launch_expand(const char* fn, int r, vk::ExpandArgs& a, hipStream_t st) {
+int launch_expand(const char* fn, int r, vk::ExpandArgs& a, hipStream_t st, const vk::ExpandDrop* d = nullptr) {
     int64_t blocks = 0;
     for (int i = 0; i < a.n; ++i) {
         a.start[i] = (int)blocks;
@@ -347,33 +445,61 @@ int launch_expand(const char* fn, int r, vk::ExpandArgs& a, hipStream_t st) {
     a.start[a.n] = (int)blocks;
     if (!blocks) return 0;
     if (blocks > 0x7FFFFFFF) return vk::set_error("%s: too many rows", fn);
-    launch_by_r(r, vk::lora_expand_kernel<4>, vk::lora_expand_kernel<8>, vk::lora_expand_kernel<16>, vk::lora_expand_kernel<32>, (int)blocks, 0, st, a);
+    if (d)
+        launch_by_r(r, vk::lora_expand_kernel<4, vk::ExpandDrop>, vk::lora_expand_kernel<8, vk::ExpandDrop>, vk::lora_expand_kernel<16, vk::ExpandDrop>, vk::lora_expand_kernel<32, vk::ExpandDrop>,
+                    (int)blocks, 0, st, a, *d);
+    else
+        launch_by_r(r, vk::lora_expand_kernel<4>, vk::lora_expand_kernel<8>, vk::lora_expand_kernel<16>, vk::lora_expand_kernel<32>, (int)blocks, 0, st, a);
     return vk::check_launch(fn);
 }
 
-}  // namespace
+int launch_colpartial(const char* fn, int r, vk::ColpArgs& cp, hipStream_t st, const vk::ColpDrop* d) {
+    int blocks = 0;
+    for (int i = 0; i < cp.n; ++i) { cp.start[i] = blocks; blocks += cp.job[i].nblk * (cp.job[i].ncols / vk::COLP_COLS); }
+    cp.start[cp.n] = blocks;
+    if (!blocks) return 0;
+    if (d)
+        launch_by_r(r, vk::lora_colpartial_kernel<4, vk::ColpDrop>, vk::lora_colpartial_kernel<8, vk::ColpDrop>, vk::lora_colpartial_kernel<16, vk::ColpDrop>,
+                    vk::lora_colpartial_kernel<32, vk::ColpDrop>, blocks, 0, st, cp, *d);
+    else
+        launch_by_r(r, vk::lora_colpartial_kernel<4>, vk::lora_colpartial_kernel<8>, vk::lora_colpartial_kernel<16>, vk::lora_colpartial_kernel<32>,
+                    blocks, 0, st, cp);
+    return vk::check_launch(fn);
+}
 
-extern "C" int vk_lora_fwd(const vk_lora_problem* p, int n, vk_stream_t s) {
-    if (!p || n < 1 || n > VK_LORA_MAX_PROBLEMS) return vk::set_error("vk_lora_fwd: %d problems (1 .. %d)", n, VK_LORA_MAX_PROBLEMS);
+// vk_lora_fwd (drop NULL) and vk_lora_fwd_drop: the masked kernels run only when a problem has a threshold
+int lora_fwd(const char* fn, const vk_lora_problem* p, const vk_dropout* drop, int n, vk_stream_t s) {
+    if (!p || n < 1 || n > VK_LORA_MAX_PROBLEMS) return vk::set_error("%s: %d problems (1 .. %d)", fn, n, VK_LORA_MAX_PROBLEMS);
     vk::RowdotArgs rd = {};
+    vk::RowdotDrop rdd = {};
     vk::ExpandArgs ex = {};
     int maxK = 0;
     for (int i = 0; i < n; ++i) {
         const vk_lora_problem& q = p[i];
         const void* ptrs[5] = {q.X, q.A, q.B, q.T, q.Y};
-        if (check_common("vk_lora_fwd", i, q.M, q.K, q.N, q.r, q.ldx, q.ldy, ptrs, 5)) return -1;
-        if (q.r != p[0].r) return vk::set_error("vk_lora_fwd: problem %d: r = %d, problem 0 has %d (one rank per call)", i, q.r, p[0].r);
+        if (check_common(fn, i, q.M, q.K, q.N, q.r, q.ldx, q.ldy, ptrs, 5)) return -1;
+        if (q.r != p[0].r) return vk::set_error("%s: problem %d: r = %d, problem 0 has %d (one rank per call)", fn, i, q.r, p[0].r);
         for (int k = 0; k < i; ++k)
-            if (p[k].Y == q.Y || p[k].T == q.T) return vk::set_error("vk_lora_fwd: problems %d and %d write the same T or Y", k, i);
-        rd.job[i] = vk::RowdotJob{(const uint16_t*)q.X, (const uint16_t*)q.A, (uint16_t*)q.T, q.dyn, q.M, q.K, q.ldx, q.K, 1, 1.0f};
+            if (p[k].Y == q.Y || p[k].T == q.T) return vk::set_error("%s: problems %d and %d write the same T or Y", fn, k, i);
+        rdd.d[i] = drop_cfg(drop, i);
+        rd.job[i] = vk::RowdotJob{(const uint16_t*)q.X, (const uint16_t*)q.A, (uint16_t*)q.T, q.dyn, q.M, q.K, q.ldx, q.K, 1, rdd.d[i].scale};
         vk::ExpandJob& e = ex.job[i];
         e.out = (uint16_t*)q.Y; e.dyn = q.dyn; e.M = q.M; e.ncols = q.N; e.ldo = q.ldy; e.nmem = 1;
         e.mem[0] = vk::ExpandMember{(const uint16_t*)q.T, (const uint16_t*)q.B, q.scale, 0};
         if (q.K > maxK) maxK = q.K;
     }
     rd.n = ex.n = n;
-    if (launch_rowdot("vk_lora_fwd (T)", p[0].r, rd, maxK, (hipStream_t)s)) return -1;
+    if (launch_rowdot("vk_lora_fwd (T)", p[0].r, rd, maxK, (hipStream_t)s, any_drop(drop, n) ? &rdd : nullptr)) return -1;
     return launch_expand("vk_lora_fwd (expand)", p[0].r, ex, (hipStream_t)s);
+}
+
+}  // namespace
+
+extern "C" int vk_lora_fwd(const vk_lora_problem* p, int n, vk_stream_t s) { return lora_fwd("vk_lora_fwd", p, nullptr, n, s); }
+extern "C" int vk_lora_fwd_drop(const vk_lora_problem* p, const vk_dropout* drop, int n, vk_stream_t s) {
+    if (!p || n < 1 || n > VK_LORA_MAX_PROBLEMS) return vk::set_error("vk_lora_fwd_drop: %d problems (1 .. %d)", n, VK_LORA_MAX_PROBLEMS);
+    if (check_drop("vk_lora_fwd_drop", drop, n)) return -1;
+    return lora_fwd("vk_lora_fwd_drop", p, drop, n, s);
 }
 
 extern "C" int64_t vk_lora_bwd_work_bytes(const vk_lora_bwd_problem* p, int n) {
@@ -386,28 +512,32 @@ extern "C" int64_t vk_lora_bwd_work_bytes(const vk_lora_bwd_problem* p, int n) {
     return total > 0 ? total : 256;
 }
 
-extern "C" int vk_lora_bwd(const vk_lora_bwd_problem* p, int n, void* work, vk_stream_t s) {
-    if (!p || n < 1 || n > VK_LORA_MAX_PROBLEMS) return vk::set_error("vk_lora_bwd: %d problems (1 .. %d)", n, VK_LORA_MAX_PROBLEMS);
-    if (!work || ((uintptr_t)work & 15)) return vk::set_error("vk_lora_bwd: the workspace must be a 16-byte aligned buffer of vk_lora_bwd_work_bytes()");
+namespace {
+int lora_bwd(const char* fn, const vk_lora_bwd_problem* p, const vk_dropout* drop, int n, void* work, vk_stream_t s) {
+    if (!p || n < 1 || n > VK_LORA_MAX_PROBLEMS) return vk::set_error("%s: %d problems (1 .. %d)", fn, n, VK_LORA_MAX_PROBLEMS);
+    if (!work || ((uintptr_t)work & 15)) return vk::set_error("%s: the workspace must be a 16-byte aligned buffer of vk_lora_bwd_work_bytes()", fn);
     hipStream_t st = (hipStream_t)s;
     vk::RowdotArgs rd = {};
     vk::ColpArgs cp = {};
+    vk::ColpDrop cpd = {};
     vk::ReduceArgs re = {};
     vk::ExpandArgs ex = {};
+    vk::ExpandDrop exd = {};
+    const bool masked = any_drop(drop, n);
     const int r = p[0].r;
     int maxN = 0;
     char* w = (char*)work;
     for (int i = 0; i < n; ++i) {
         const vk_lora_bwd_problem& q = p[i];
         const void* ptrs[6] = {q.X, q.A, q.B, q.T, q.dY, q.dT};
-        if (check_common("vk_lora_bwd", i, q.M, q.K, q.N, q.r, q.ldx, q.ldy, ptrs, 6)) return -1;
+        if (check_common(fn, i, q.M, q.K, q.N, q.r, q.ldx, q.ldy, ptrs, 6)) return -1;
         if (!q.dA != !q.dB || ((uintptr_t)q.dA & 15) || ((uintptr_t)q.dB & 15))
-            return vk::set_error("vk_lora_bwd: problem %d: dA and dB are both set (16-byte aligned) or both NULL (a frozen adapter)", i);
-        if (!q.dA && !q.dX) return vk::set_error("vk_lora_bwd: problem %d has no output (dA, dB and dX are NULL)", i);
-        if (q.r != r) return vk::set_error("vk_lora_bwd: problem %d: r = %d, problem 0 has %d (one rank per call)", i, q.r, r);
-        if (q.dX && (((uintptr_t)q.dX & 15) || q.lddx < q.K || q.lddx % 8)) return vk::set_error("vk_lora_bwd: problem %d: dX alignment / lddx %d", i, q.lddx);
+            return vk::set_error("%s: problem %d: dA and dB are both set (16-byte aligned) or both NULL (a frozen adapter)", fn, i);
+        if (!q.dA && !q.dX) return vk::set_error("%s: problem %d has no output (dA, dB and dX are NULL)", fn, i);
+        if (q.r != r) return vk::set_error("%s: problem %d: r = %d, problem 0 has %d (one rank per call)", fn, i, q.r, r);
+        if (q.dX && (((uintptr_t)q.dX & 15) || q.lddx < q.K || q.lddx % 8)) return vk::set_error("%s: problem %d: dX alignment / lddx %d", fn, i, q.lddx);
         for (int k = 0; k < i; ++k)
-            if (p[k].dT == q.dT) return vk::set_error("vk_lora_bwd: problems %d and %d write the same dT", k, i);
+            if (p[k].dT == q.dT) return vk::set_error("%s: problems %d and %d write the same dT", fn, k, i);
         rd.job[i] = vk::RowdotJob{(const uint16_t*)q.dY, (const uint16_t*)q.B, (uint16_t*)q.dT, q.dyn, q.M, q.N, q.ldy, 1, q.r, q.scale};
         if (q.N > maxN) maxN = q.N;
         // partial records: dB [nblk][N][r], then dA [nblk][r][K]
@@ -415,8 +545,10 @@ extern "C" int vk_lora_bwd(const vk_lora_bwd_problem* p, int n, void* work, vk_s
         float* partB = (float*)w;
         float* partA = partB + (size_t)nblk * q.N * q.r;
         w += round256((int64_t)nblk * q.r * ((int64_t)q.K + q.N) * 4);
+        const vk::DropCfg dc = drop_cfg(drop, i);
         if (q.dA) {
         cp.job[cp.n++] = vk::ColpJob{(const uint16_t*)q.dY, (const uint16_t*)q.T, partB, q.dyn, q.M, q.N, q.ldy, q.r, 1, nblk};
+        cpd.d[cp.n] = dc;                // the dA job that follows: X is masked as the forward masked it
         cp.job[cp.n++] = vk::ColpJob{(const uint16_t*)q.X, (const uint16_t*)q.dT, partA, q.dyn, q.M, q.K, q.ldx, 1, q.K, nblk};
         // gradient jobs: the problems of one adapter (a shared sub-layer's two streams) are summed by ONE job, in list order
         int g = -1;
@@ -428,12 +560,12 @@ extern "C" int vk_lora_bwd(const vk_lora_bwd_problem* p, int n, void* work, vk_s
             re.job[g].dst = q.dB; re.job[g].n = q.N * q.r; re.job[g].accumulate = q.accumulate != 0;
             re.job[g + 1].dst = q.dA; re.job[g + 1].n = q.r * q.K; re.job[g + 1].accumulate = q.accumulate != 0;
         } else {
-            if (!q.accumulate) return vk::set_error("vk_lora_bwd: problem %d writes the gradients of an earlier problem without `accumulate`", i);
+            if (!q.accumulate) return vk::set_error("%s: problem %d writes the gradients of an earlier problem without `accumulate`", fn, i);
             if (re.job[g + 1].dst != q.dA || re.job[g].n != q.N * q.r || re.job[g + 1].n != q.r * q.K || re.job[g].nmem >= 2)
-                return vk::set_error("vk_lora_bwd: problem %d: a shared adapter has one dA, one dB and at most two sources", i);
+                return vk::set_error("%s: problem %d: a shared adapter has one dA, one dB and at most two sources", fn, i);
         }
         re.job[g].mem[re.job[g].nmem++] = vk::ReduceMember{partB, nblk, q.scale};
-        re.job[g + 1].mem[re.job[g + 1].nmem++] = vk::ReduceMember{partA, nblk, 1.0f};
+        re.job[g + 1].mem[re.job[g + 1].nmem++] = vk::ReduceMember{partA, nblk, dc.scale};      // 1 / (1 - p) on this problem's finished sum
         }
         if (q.dX) {
             int e = -1;
@@ -446,25 +578,17 @@ extern "C" int vk_lora_bwd(const vk_lora_bwd_problem* p, int n, void* work, vk_s
             }
             vk::ExpandJob& j = ex.job[e];
             if (j.M != q.M || j.ncols != q.K || j.ldo != q.lddx || j.dyn != q.dyn || j.nmem >= 3)
-                return vk::set_error("vk_lora_bwd: problem %d: the (at most 3) adapters that add into one dX share its shape", i);
-            j.mem[j.nmem++] = vk::ExpandMember{(const uint16_t*)q.dT, (const uint16_t*)q.A, 1.0f, 1};
+                return vk::set_error("%s: problem %d: the (at most 3) adapters that add into one dX share its shape", fn, i);
+            exd.d[e][j.nmem] = dc;
+            j.mem[j.nmem++] = vk::ExpandMember{(const uint16_t*)q.dT, (const uint16_t*)q.A, dc.scale, 1};
         }
     }
     for (int i = 0; i < n; ++i)          // no gradient may alias another job's: dA of one adapter is nobody's dB
         for (int k = 0; k < n; ++k)
-            if (p[i].dA && p[i].dA == p[k].dB) return vk::set_error("vk_lora_bwd: dA of problem %d is dB of problem %d", i, k);
+            if (p[i].dA && p[i].dA == p[k].dB) return vk::set_error("%s: dA of problem %d is dB of problem %d", fn, i, k);
     rd.n = n;
     if (launch_rowdot("vk_lora_bwd (dT)", r, rd, maxN, st)) return -1;
-    {
-        int blocks = 0;
-        for (int i = 0; i < cp.n; ++i) { cp.start[i] = blocks; blocks += cp.job[i].nblk * (cp.job[i].ncols / vk::COLP_COLS); }
-        cp.start[cp.n] = blocks;
-        if (blocks) {
-            launch_by_r(r, vk::lora_colpartial_kernel<4>, vk::lora_colpartial_kernel<8>, vk::lora_colpartial_kernel<16>, vk::lora_colpartial_kernel<32>,
-                        blocks, 0, st, cp);
-            if (vk::check_launch("vk_lora_bwd (partials)")) return -1;
-        }
-    }
+    if (launch_colpartial("vk_lora_bwd (partials)", r, cp, st, masked ? &cpd : nullptr)) return -1;
     {
         int blocks = 0;
         for (int i = 0; i < re.n; ++i) { re.start[i] = blocks; blocks += (re.job[i].n + 255) / 256; }
@@ -474,9 +598,18 @@ extern "C" int vk_lora_bwd(const vk_lora_bwd_problem* p, int n, void* work, vk_s
             if (vk::check_launch("vk_lora_bwd (reduce)")) return -1;
         }
     }
-    if (ex.n) return launch_expand("vk_lora_bwd (dX)", r, ex, st);
+    if (ex.n) return launch_expand("vk_lora_bwd (dX)", r, ex, st, masked ? &exd : nullptr);
     return 0;
 }
+}  // namespace
+
+extern "C" int vk_lora_bwd(const vk_lora_bwd_problem* p, int n, void* work, vk_stream_t s) { return lora_bwd("vk_lora_bwd", p, nullptr, n, work, s); }
+extern "C" int vk_lora_bwd_drop(const vk_lora_bwd_problem* p, const vk_dropout* drop, int n, void* work, vk_stream_t s) {
+    if (!p || n < 1 || n > VK_LORA_MAX_PROBLEMS) return vk::set_error("vk_lora_bwd_drop: %d problems (1 .. %d)", n, VK_LORA_MAX_PROBLEMS);
+    if (check_drop("vk_lora_bwd_drop", drop, n)) return -1;
+    return lora_bwd("vk_lora_bwd_drop", p, drop, n, work, s);
+}
+
 
 // ================================================================================================ whole projections
 // vk_lora_proj_fwd / vk_lora_proj_bwd: adapters on the attention output and the two feed-forward projections, K or N up to 4096
@@ -494,8 +627,9 @@ constexpr int PROJ_MAX_DIM = 4096;
 // Row groups of 4 rows per wave whose accumulators stay in registers: IT * 4 * R <= 128 floats per lane
 template <int R> struct ProjRowdot { static constexpr int IT = 32 / R > 4 ? 4 : 32 / R; static constexpr int ROWS = 16 * IT; };
 
-template <int R>
-__global__ __launch_bounds__(256) void lora_rowdot_chunked_kernel(const RowdotArgs a) {
+template <int R, typename... D>
+__global__ __launch_bounds__(256) void lora_rowdot_chunked_kernel(const RowdotArgs a, const D... d) {
+    constexpr bool DROP = sizeof...(D) == 1;
     constexpr int RW = 4, V = RW * R, OWN = V / 64 > 1 ? V / 64 : 1, IT = ProjRowdot<R>::IT, ROWS = ProjRowdot<R>::ROWS;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     uint16_t* Qs = (uint16_t*)smem;                  // [R][CH]
@@ -507,6 +641,12 @@ __global__ __launch_bounds__(256) void lora_rowdot_chunked_kernel(const RowdotAr
     if (row0 >= rows) return;                        // the whole workgroup: no barrier is left waiting
     const int CH = Kc < PROJ_CHUNK ? Kc : PROJ_CHUNK;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    DropCfg dc = {};
+    uint64_t seed = 0;
+    if constexpr (DROP) {
+        dc = the_drop(d...).d[p];
+        if (dc.thr) seed = *dc.seed;
+    }
     float acc[IT][V];
 #pragma unroll
     for (int it = 0; it < IT; ++it)
@@ -531,6 +671,12 @@ __global__ __launch_bounds__(256) void lora_rowdot_chunked_kernel(const RowdotAr
                     u32x4 x[RW];
 #pragma unroll
                     for (int i = 0; i < RW; ++i) x[i] = *(const u32x4*)(prow[i] + k0);
+                    if constexpr (DROP) {
+                        if (dc.thr) {
+#pragma unroll
+                            for (int i = 0; i < RW; ++i) x[i] &= keep_mask8(dc, seed, uniform32((uint32_t)(m0 + i)), (uint32_t)(c0 + k0));
+                        }
+                    }
 #pragma unroll
                     for (int j = 0; j < R; ++j) {
                         const u32x4 q = *(const u32x4*)(Qs + j * CH + k0);
@@ -567,8 +713,9 @@ struct ProjExpandJob {
 };
 struct ProjExpandArgs { ProjExpandJob job[LORA_MAXP]; int start[LORA_MAXP + 1]; int n; };
 
-template <int R>
-__global__ __launch_bounds__(256) void lora_proj_expand_kernel(const ProjExpandArgs a) {
+template <int R, typename... D>
+__global__ __launch_bounds__(256) void lora_proj_expand_kernel(const ProjExpandArgs a, const D... d) {
+    constexpr bool DROP = sizeof...(D) == 1;
     constexpr int JC = R < 8 ? R : 8;
     int p = 0;
     while (p + 1 < a.n && (int)blockIdx.x >= a.start[p + 1]) ++p;
@@ -617,6 +764,21 @@ __global__ __launch_bounds__(256) void lora_proj_expand_kernel(const ProjExpandA
                 }
             }
         }
+        if constexpr (DROP) {
+            const DropCfg dc = the_drop(d...).d[p][c];
+            if (dc.thr) {
+                const uint64_t seed = *dc.seed;
+#pragma unroll
+                for (int i = 0; i < EXPAND_RPT; ++i) {
+                    if (i < nr) {
+                        const u32x4 km = keep_mask8(dc, seed, (uint32_t)(m0 + i), (uint32_t)x);
+#pragma unroll
+                        for (int e = 0; e < 8; ++e)
+                            if (!(km[e >> 1] & (e & 1 ? 0x10000u : 1u))) part[i][e] = 0.f;
+                    }
+                }
+            }
+        }
 #pragma unroll
         for (int i = 0; i < EXPAND_RPT; ++i)
 #pragma unroll
@@ -656,7 +818,7 @@ namespace {
 
 int proj_rowdot_rows(int r) { return r == 4 ? vk::ProjRowdot<4>::ROWS : r == 8 ? vk::ProjRowdot<8>::ROWS : r == 16 ? vk::ProjRowdot<16>::ROWS : vk::ProjRowdot<32>::ROWS; }
 
-int launch_rowdot_chunked(const char* fn, int r, vk::RowdotArgs& a, int maxK, hipStream_t st) {
+int launch_rowdot_chunked(const char* fn, int r, vk::RowdotArgs& a, int maxK, hipStream_t st, const vk::RowdotDrop* d = nullptr) {
     const int per = proj_rowdot_rows(r);
     int blocks = 0;
     for (int i = 0; i < a.n; ++i) { a.start[i] = blocks; blocks += (a.job[i].M + per - 1) / per; }
@@ -669,12 +831,23 @@ int launch_rowdot_chunked(const char* fn, int r, vk::RowdotArgs& a, int maxK, hi
         hipFuncSetAttribute((const void*)vk::lora_rowdot_chunked_kernel<32>, hipFuncAttributeMaxDynamicSharedMemorySize, 32 * vk::PROJ_CHUNK * 2)};
     (void)attr;
     const int ch = maxK < vk::PROJ_CHUNK ? maxK : vk::PROJ_CHUNK;          // every job's chunk stride is min(its Kc, PROJ_CHUNK) <= this
+    if (d) {
+        static const hipError_t attr_d[4] = {
+            hipFuncSetAttribute((const void*)vk::lora_rowdot_chunked_kernel<4, vk::RowdotDrop>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * vk::PROJ_CHUNK * 2),
+            hipFuncSetAttribute((const void*)vk::lora_rowdot_chunked_kernel<8, vk::RowdotDrop>, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * vk::PROJ_CHUNK * 2),
+            hipFuncSetAttribute((const void*)vk::lora_rowdot_chunked_kernel<16, vk::RowdotDrop>, hipFuncAttributeMaxDynamicSharedMemorySize, 16 * vk::PROJ_CHUNK * 2),
+            hipFuncSetAttribute((const void*)vk::lora_rowdot_chunked_kernel<32, vk::RowdotDrop>, hipFuncAttributeMaxDynamicSharedMemorySize, 32 * vk::PROJ_CHUNK * 2)};
+        (void)attr_d;
+        launch_by_r(r, vk::lora_rowdot_chunked_kernel<4, vk::RowdotDrop>, vk::lora_rowdot_chunked_kernel<8, vk::RowdotDrop>, vk::lora_rowdot_chunked_kernel<16, vk::RowdotDrop>,
+                    vk::lora_rowdot_chunked_kernel<32, vk::RowdotDrop>, blocks, (size_t)r * ch * 2, st, a, *d);
+        return vk::check_launch(fn);
+    }
     launch_by_r(r, vk::lora_rowdot_chunked_kernel<4>, vk::lora_rowdot_chunked_kernel<8>, vk::lora_rowdot_chunked_kernel<16>,
                 vk::lora_rowdot_chunked_kernel<32>, blocks, (size_t)r * ch * 2, st, a);
     return vk::check_launch(fn);
 }
 
-int launch_proj_expand(const char* fn, int r, vk::ProjExpandArgs& a, hipStream_t st) {
+int launch_proj_expand(const char* fn, int r, vk::ProjExpandArgs& a, hipStream_t st, const vk::ExpandDrop* d = nullptr) {
     int64_t blocks = 0;
     for (int i = 0; i < a.n; ++i) {
         a.start[i] = (int)blocks;
@@ -684,8 +857,12 @@ int launch_proj_expand(const char* fn, int r, vk::ProjExpandArgs& a, hipStream_t
     a.start[a.n] = (int)blocks;
     if (!blocks) return 0;
     if (blocks > 0x7FFFFFFF) return vk::set_error("%s: too many rows", fn);
-    launch_by_r(r, vk::lora_proj_expand_kernel<4>, vk::lora_proj_expand_kernel<8>, vk::lora_proj_expand_kernel<16>, vk::lora_proj_expand_kernel<32>,
-                (int)blocks, 0, st, a);
+    if (d)
+        launch_by_r(r, vk::lora_proj_expand_kernel<4, vk::ExpandDrop>, vk::lora_proj_expand_kernel<8, vk::ExpandDrop>, vk::lora_proj_expand_kernel<16, vk::ExpandDrop>,
+                    vk::lora_proj_expand_kernel<32, vk::ExpandDrop>, (int)blocks, 0, st, a, *d);
+    else
+        launch_by_r(r, vk::lora_proj_expand_kernel<4>, vk::lora_proj_expand_kernel<8>, vk::lora_proj_expand_kernel<16>, vk::lora_proj_expand_kernel<32>,
+                    (int)blocks, 0, st, a);
     return vk::check_launch(fn);
 }
 
@@ -702,26 +879,26 @@ int check_proj(const char* fn, int i, int M, int K, int N, int r, int ldx, int l
     return 0;
 }
 
-}  // namespace
-
-extern "C" int vk_lora_proj_fwd(const vk_lora_proj_problem* p, int n, vk_stream_t s) {
-    if (!p || n < 1 || n > VK_LORA_MAX_PROBLEMS) return vk::set_error("vk_lora_proj_fwd: %d problems (1 .. %d)", n, VK_LORA_MAX_PROBLEMS);
+int lora_proj_fwd(const char* fn, const vk_lora_proj_problem* p, const vk_dropout* drop, int n, vk_stream_t s) {
+    if (!p || n < 1 || n > VK_LORA_MAX_PROBLEMS) return vk::set_error("%s: %d problems (1 .. %d)", fn, n, VK_LORA_MAX_PROBLEMS);
     vk::RowdotArgs rd = {};
+    vk::RowdotDrop rdd = {};
     vk::ProjExpandArgs ex = {};
     int maxK = 0;
     for (int i = 0; i < n; ++i) {
         const vk_lora_proj_problem& q = p[i];
         const void* ptrs[5] = {q.X, q.A, q.B, q.T, q.Y};
-        if (check_proj("vk_lora_proj_fwd", i, q.M, q.K, q.N, q.r, q.ldx, q.ldy, ptrs, 5)) return -1;
-        if (q.r != p[0].r) return vk::set_error("vk_lora_proj_fwd: problem %d: r = %d, problem 0 has %d (one rank per call)", i, q.r, p[0].r);
-        if (q.act != 0 && q.act != 1) return vk::set_error("vk_lora_proj_fwd: problem %d: act = %d (0 or 1)", i, q.act);
-        if (q.act == 0 && q.G) return vk::set_error("vk_lora_proj_fwd: problem %d: act = 0 takes no G", i);
+        if (check_proj(fn, i, q.M, q.K, q.N, q.r, q.ldx, q.ldy, ptrs, 5)) return -1;
+        if (q.r != p[0].r) return vk::set_error("%s: problem %d: r = %d, problem 0 has %d (one rank per call)", fn, i, q.r, p[0].r);
+        if (q.act != 0 && q.act != 1) return vk::set_error("%s: problem %d: act = %d (0 or 1)", fn, i, q.act);
+        if (q.act == 0 && q.G) return vk::set_error("%s: problem %d: act = 0 takes no G", fn, i);
         if (q.act == 1 && (!q.G || ((uintptr_t)q.G & 15) || q.ldg < q.N || q.ldg % 8))
-            return vk::set_error("vk_lora_proj_fwd: problem %d: act = 1 needs G (16-byte aligned, ldg %d a multiple of 8, >= N)", i, q.ldg);
+            return vk::set_error("%s: problem %d: act = 1 needs G (16-byte aligned, ldg %d a multiple of 8, >= N)", fn, i, q.ldg);
         for (int k = 0; k < i; ++k)
             if (p[k].Y == q.Y || p[k].T == q.T || (q.G && p[k].G == q.G))
-                return vk::set_error("vk_lora_proj_fwd: problems %d and %d write the same T, Y or G", k, i);
-        rd.job[i] = vk::RowdotJob{(const uint16_t*)q.X, (const uint16_t*)q.A, (uint16_t*)q.T, q.dyn, q.M, q.K, q.ldx, q.K, 1, 1.0f};
+                return vk::set_error("%s: problems %d and %d write the same T, Y or G", fn, k, i);
+        rdd.d[i] = drop_cfg(drop, i);
+        rd.job[i] = vk::RowdotJob{(const uint16_t*)q.X, (const uint16_t*)q.A, (uint16_t*)q.T, q.dyn, q.M, q.K, q.ldx, q.K, 1, rdd.d[i].scale};
         vk::ProjExpandJob& e = ex.job[i];
         e.out = (uint16_t*)q.Y; e.dyn = q.dyn; e.rho = nullptr; e.G = (uint16_t*)q.G; e.M = q.M; e.ncols = q.N; e.ldo = q.ldy; e.ldr = 0; e.ldg = q.ldg;
         e.nmem = 1;
@@ -729,8 +906,17 @@ extern "C" int vk_lora_proj_fwd(const vk_lora_proj_problem* p, int n, vk_stream_
         if (q.K > maxK) maxK = q.K;
     }
     rd.n = ex.n = n;
-    if (launch_rowdot_chunked("vk_lora_proj_fwd (T)", p[0].r, rd, maxK, (hipStream_t)s)) return -1;
+    if (launch_rowdot_chunked("vk_lora_proj_fwd (T)", p[0].r, rd, maxK, (hipStream_t)s, any_drop(drop, n) ? &rdd : nullptr)) return -1;
     return launch_proj_expand("vk_lora_proj_fwd (expand)", p[0].r, ex, (hipStream_t)s);
+}
+
+}  // namespace
+
+extern "C" int vk_lora_proj_fwd(const vk_lora_proj_problem* p, int n, vk_stream_t s) { return lora_proj_fwd("vk_lora_proj_fwd", p, nullptr, n, s); }
+extern "C" int vk_lora_proj_fwd_drop(const vk_lora_proj_problem* p, const vk_dropout* drop, int n, vk_stream_t s) {
+    if (!p || n < 1 || n > VK_LORA_MAX_PROBLEMS) return vk::set_error("vk_lora_proj_fwd_drop: %d problems (1 .. %d)", n, VK_LORA_MAX_PROBLEMS);
+    if (check_drop("vk_lora_proj_fwd_drop", drop, n)) return -1;
+    return lora_proj_fwd("vk_lora_proj_fwd_drop", p, drop, n, s);
 }
 
 extern "C" int64_t vk_lora_proj_bwd_work_bytes(const vk_lora_proj_bwd_problem* p, int n) {
@@ -743,15 +929,18 @@ extern "C" int64_t vk_lora_proj_bwd_work_bytes(const vk_lora_proj_bwd_problem* p
     return total > 0 ? total : 256;
 }
 
-extern "C" int vk_lora_proj_bwd(const vk_lora_proj_bwd_problem* p, int n, void* work, vk_stream_t s) {
-    const char* fn = "vk_lora_proj_bwd";
+namespace {
+int lora_proj_bwd(const char* fn, const vk_lora_proj_bwd_problem* p, const vk_dropout* drop, int n, void* work, vk_stream_t s) {
     if (!p || n < 1 || n > VK_LORA_MAX_PROBLEMS) return vk::set_error("%s: %d problems (1 .. %d)", fn, n, VK_LORA_MAX_PROBLEMS);
     if (!work || ((uintptr_t)work & 15)) return vk::set_error("%s: the workspace must be a 16-byte aligned buffer of vk_lora_proj_bwd_work_bytes()", fn);
     hipStream_t st = (hipStream_t)s;
     vk::RowdotArgs rd = {};
     vk::ColpArgs cp = {};
+    vk::ColpDrop cpd = {};
     vk::ReduceArgs re = {};
     vk::ProjExpandArgs ex = {};
+    vk::ExpandDrop exd = {};
+    const bool masked = any_drop(drop, n);
     const int r = p[0].r;
     int maxN = 0;
     char* w = (char*)work;
@@ -774,8 +963,10 @@ extern "C" int vk_lora_proj_bwd(const vk_lora_proj_bwd_problem* p, int n, void* 
         float* partB = (float*)w;
         float* partA = partB + (size_t)nblk * q.N * q.r;
         w += round256((int64_t)nblk * q.r * ((int64_t)q.K + q.N) * 4);
+        const vk::DropCfg dc = drop_cfg(drop, i);
         if (q.dA) {
             cp.job[cp.n++] = vk::ColpJob{(const uint16_t*)q.dY, (const uint16_t*)q.T, partB, q.dyn, q.M, q.N, q.ldy, q.r, 1, nblk};
+            cpd.d[cp.n] = dc;                // the dA job that follows: X is masked as the forward masked it
             cp.job[cp.n++] = vk::ColpJob{(const uint16_t*)q.X, (const uint16_t*)q.dT, partA, q.dyn, q.M, q.K, q.ldx, 1, q.K, nblk};
             // gradient jobs: the problems of one adapter (a shared sub-layer's two streams) are summed by ONE job, in list order
             int g = -1;
@@ -792,7 +983,7 @@ extern "C" int vk_lora_proj_bwd(const vk_lora_proj_bwd_problem* p, int n, void* 
                     return vk::set_error("%s: problem %d: a shared adapter has one dA, one dB and at most two sources", fn, i);
             }
             re.job[g].mem[re.job[g].nmem++] = vk::ReduceMember{partB, nblk, q.scale};
-            re.job[g + 1].mem[re.job[g + 1].nmem++] = vk::ReduceMember{partA, nblk, 1.0f};
+            re.job[g + 1].mem[re.job[g + 1].nmem++] = vk::ReduceMember{partA, nblk, dc.scale};      // 1 / (1 - p) on this problem's finished sum
         }
         if (q.dX) {
             int e = -1;
@@ -809,7 +1000,8 @@ extern "C" int vk_lora_proj_bwd(const vk_lora_proj_bwd_problem* p, int n, void* 
                 return vk::set_error("%s: problem %d: the adapters that add into one dX name one R (and ldr)", fn, i);
             if (j.M != q.M || j.ncols != q.K || j.ldo != q.lddx || j.dyn != q.dyn || j.nmem >= 3)
                 return vk::set_error("%s: problem %d: the (at most 3) adapters that add into one dX share its shape", fn, i);
-            j.mem[j.nmem++] = vk::ExpandMember{(const uint16_t*)q.dT, (const uint16_t*)q.A, 1.0f, 1};
+            exd.d[e][j.nmem] = dc;
+            j.mem[j.nmem++] = vk::ExpandMember{(const uint16_t*)q.dT, (const uint16_t*)q.A, dc.scale, 1};
         }
     }
     for (int i = 0; i < n; ++i)          // no gradient may alias another job's: dA of one adapter is nobody's dB
@@ -817,16 +1009,7 @@ extern "C" int vk_lora_proj_bwd(const vk_lora_proj_bwd_problem* p, int n, void* 
             if (p[i].dA && p[i].dA == p[k].dB) return vk::set_error("%s: dA of problem %d is dB of problem %d", fn, i, k);
     rd.n = n;
     if (launch_rowdot_chunked("vk_lora_proj_bwd (dT)", r, rd, maxN, st)) return -1;
-    {
-        int blocks = 0;
-        for (int i = 0; i < cp.n; ++i) { cp.start[i] = blocks; blocks += cp.job[i].nblk * (cp.job[i].ncols / vk::COLP_COLS); }
-        cp.start[cp.n] = blocks;
-        if (blocks) {
-            launch_by_r(r, vk::lora_colpartial_kernel<4>, vk::lora_colpartial_kernel<8>, vk::lora_colpartial_kernel<16>, vk::lora_colpartial_kernel<32>,
-                        blocks, 0, st, cp);
-            if (vk::check_launch("vk_lora_proj_bwd (partials)")) return -1;
-        }
-    }
+    if (launch_colpartial("vk_lora_proj_bwd (partials)", r, cp, st, masked ? &cpd : nullptr)) return -1;
     {
         int blocks = 0;
         for (int i = 0; i < re.n; ++i) { re.start[i] = blocks; blocks += (re.job[i].n + 255) / 256; }
@@ -836,6 +1019,16 @@ extern "C" int vk_lora_proj_bwd(const vk_lora_proj_bwd_problem* p, int n, void* 
             if (vk::check_launch("vk_lora_proj_bwd (reduce)")) return -1;
         }
     }
-    if (ex.n) return launch_proj_expand("vk_lora_proj_bwd (dX)", r, ex, st);
+    if (ex.n) return launch_proj_expand("vk_lora_proj_bwd (dX)", r, ex, st, masked ? &exd : nullptr);
     return 0;
+}
+}  // namespace
+
+extern "C" int vk_lora_proj_bwd(const vk_lora_proj_bwd_problem* p, int n, void* work, vk_stream_t s) {
+    return lora_proj_bwd("vk_lora_proj_bwd", p, nullptr, n, work, s);
+}
+extern "C" int vk_lora_proj_bwd_drop(const vk_lora_proj_bwd_problem* p, const vk_dropout* drop, int n, void* work, vk_stream_t s) {
+    if (!p || n < 1 || n > VK_LORA_MAX_PROBLEMS) return vk::set_error("vk_lora_proj_bwd_drop: %d problems (1 .. %d)", n, VK_LORA_MAX_PROBLEMS);
+    if (check_drop("vk_lora_proj_bwd_drop", drop, n)) return -1;
+    return lora_proj_bwd("vk_lora_proj_bwd_drop", p, drop, n, work, s);
 }

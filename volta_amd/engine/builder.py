@@ -102,8 +102,10 @@ class StepEngine(EmbeddingBuilders, SublayerBuilders, HeadBuilders):
 
     H8_MUL = 8.0           # static scale of the fp8 copy of the GELU output: |h| <= 56 representable, 2^-9 absolute resolution near 0
 
+    LORA_SITE_BASE = 1 << 20      # first LoRA dropout site (lora_drops): the model's own sites count up from 0 and stay far below it
+
     def __init__(self, cfg, arena, B, T, Rv, train, heads="pretrain", fp8=False, task=None, task_dropout=0.1, attn_maps=False, part=None, split=None,
-                 projection_dtype=None, frozen=None):
+                 projection_dtype=None, frozen=None, lora_dropout=0.0):
         """fp8: the forward Q|K|V, FFN-up and FFN-down projections of every sub-layer run on the e4m3 MFMA path (csrc/fp8.hip); inputs are
         quantised per row right before the GEMM, weights per output channel whenever they change; the backward stays bf16.
         heads: "pretrain" = the three pre-training heads and losses (BertForVLPreTraining); "tasks" = poolers only, the
@@ -119,7 +121,9 @@ class StepEngine(EmbeddingBuilders, SublayerBuilders, HeadBuilders):
         frozen: arena names of parameters that take no gradient (requires_grad False).  The backward list keeps an op only if its output
         reaches the gradient of a trainable parameter ("Frozen parameters"); the forward list, the buffers and, with
         nothing frozen, both lists are what they are without the argument.  A block is pruned as a whole or not at all (`frozen_blocks`),
-        so any pattern may be passed: `canonical_frozen` maps it to the one the plan depends on.  Score plans have no backward and ignore it."""
+        so any pattern may be passed: `canonical_frozen` maps it to the one the plan depends on.  Score plans have no backward and ignore it.
+        lora_dropout: the rate of the dropout on every LoRA adapter's input (volta_amd/lora.py).  A training plan with a rate > 0 runs
+        the adapters on the vk_lora_*_drop entry points; an eval plan, a score plan and a rate of 0 build what they build without it."""
         self.cfg, self.arena, self.B, self.T, self.Rv, self.train = cfg, arena, B, T, Rv, train
         self.heads = heads
         self.part, self.split = part, split
@@ -166,6 +170,10 @@ class StepEngine(EmbeddingBuilders, SublayerBuilders, HeadBuilders):
         self.keep = []
         self.fwd, self.bwd = Plan(), Plan()
         self.site = 0
+        if not 0.0 <= float(lora_dropout) < 1.0:
+            raise ValueError("lora_dropout %r: 0 <= p < 1" % (lora_dropout,))
+        self.lora_p = float(lora_dropout) if train and not self.fwd_only else 0.0
+        self.lora_site = 0            # LoRA dropout sites handed out so far (lora_drops)
         self.seed = torch.zeros(1, dtype=torch.int64, device=dev)
         self.inputs = {}              # name -> list of (struct, field) patched every step
         self.taps = {}
@@ -203,6 +211,20 @@ class StepEngine(EmbeddingBuilders, SublayerBuilders, HeadBuilders):
         site = self.site
         self.site += 1
         return L.dropout_cfg(self.seed.data_ptr(), site, p if self.train else 0.0)
+
+    def lora_drops(self, keys):
+        """{key: the dropout of one LoRA problem (one adapter on one stream)} for the problems of a sub-layer, or {} when the plan has no
+        LoRA dropout.  LoRA sites come from a counter of their own, LORA_SITE_BASE + 0, 1, ..., in the order the forward list meets the
+        problems: sub-layer by sub-layer, within a sub-layer stream by stream, within a stream target by target -- a rebuilt plan hands
+        out the same sites.  `self.site` is not advanced, so the model's own sites (and masks) are those of the model without adapters.
+        The backward problem of an adapter takes the entry of its forward problem: it replays the same stream."""
+        if not self.lora_p:
+            return {}
+        out = {}
+        for key in keys:
+            out[key] = L.dropout_cfg(self.seed.data_ptr(), self.LORA_SITE_BASE + self.lora_site, self.lora_p)
+            self.lora_site += 1
+        return out
 
     def k(self, obj):
         self.keep.append(obj)

@@ -71,7 +71,10 @@ class SublayerBuilders:
             self.gemm_fp8(f, L.EPI_BF16, [(x8_in[m] or x_in[m], wqkv(m, "master"), qkv[m], bqkv(m, "master"), None) for m in ms])
         else:
             self.gemm(f, L.NT, L.EPI_BF16, [self.prob(x_in[m], wqkv(m, "shadow"), qkv[m], self.st[m].M, 3 * Ha[m], Hm[m], Hm[m], Hm[m], 3 * Ha[m], bias=bqkv(m, "master")) for m in ms])
-        lora_T = self._lora_fwd(f, tag, lora, x_in, qkv, Hm, Ha) if lora else {}
+        # LoRA dropout: a site per problem (adapter x stream), handed out stream by stream, within a stream q, k, v, o; empty without a rate
+        have = {(m, c) for m, c, _ in lora} | {(m, "o") for m, _ in lora_o}
+        ld = self.lora_drops([(m, c) for m in ms for c in (0, 1, 2, "o") if (m, c) in have])
+        lora_T = self._lora_fwd(f, tag, lora, x_in, qkv, Hm, Ha, ld) if lora else {}
         # dropout sites in the reference's call order: tt, tv, then vv, vt (encoders.py:294-295, 309-310)
         pdrop = (cfg.attention_probs_dropout_prob, cfg.v_attention_probs_dropout_prob)
         drops = {(i, j): self.drop(pdrop[i]) for i, j in ((0, 0), (0, 1), (1, 1), (1, 0)) if gate[i][j]}
@@ -117,7 +120,7 @@ class SublayerBuilders:
             attn.append((aa, mq, gl))
         self.gemm(f, L.NT, L.EPI_BF16, [self.prob(ctx[m], self.W(names[m]["o"] + ".weight"), d[m], self.st[m].M, Hm[m], Ha[m], Ha[m], Ha[m], Hm[m], bias=self.Pm(names[m]["o"] + ".bias")) for m in ms])
         if lora_o:       # behind the output projection, in front of the tail: d += s (ctx A^T) B^T
-            To = self._lora_proj_fwd(f, tag, "o", [(m, stem, ctx[m], d[m], None) for m, stem in lora_o])
+            To = self._lora_proj_fwd(f, tag, "o", [(m, stem, ctx[m], d[m], None) for m, stem in lora_o], {m: ld[(m, "o")] for m, _ in lora_o if ld})
         tail = self._tail_fwd(tag, ms, names, d, x_in, Hm)
         if self.fwd_only:
             return []
@@ -151,7 +154,8 @@ class SublayerBuilders:
         if need_dqkv:
             self.gemm(b, L.NN, L.EPI_BF16, [self.prob(dd[m], self.W(names[m]["o"] + ".weight"), dctx[m], self.st[m].M, Ha[m], Hm[m], Hm[m], Ha[m], Ha[m]) for m in ms])
         if lora_o:       # directly behind the dd W_o dgrad: the attention backward reads the dctx this op adds to; without dqkv only dA and dB
-            self._lora_proj_bwd(b, [(m, stem, ctx[m], To[m], dd[m], dctx[m] if need_dqkv else None, None) for m, stem in lora_o])
+            self._lora_proj_bwd(b, [(m, stem, ctx[m], To[m], dd[m], dctx[m] if need_dqkv else None, None) for m, stem in lora_o],
+                                {m: ld[(m, "o")] for m, _ in lora_o if ld})
         if need_dqkv:
             for m in ms:
                 if not (gate[0][m] or gate[1][m]):       # K/V of this modality unused: their gradient is zero
@@ -172,12 +176,13 @@ class SublayerBuilders:
         self.gemm_kept(b, L.NN, L.EPI_ADDR, [self.prob(dqkv[m], wqkv(m, "shadow"), dxn[m], self.st[m].M, Hm[m], 3 * Ha[m], 3 * Ha[m], Hm[m], Hm[m], R=dz[m], ldr=Hm[m]) for m in ms],
                        [live_in[m] for m in ms])
         if lora:         # behind the last dgrad: dqkv, x_in and T are still live, dxn[m] holds the base projection's input gradient
-            self._lora_bwd(b, lora, lora_T, x_in, dqkv, dxn, live_in, Hm, Ha)
+            self._lora_bwd(b, lora, lora_T, x_in, dqkv, dxn, live_in, Hm, Ha, ld)
         return b
 
-    def _lora_fwd(self, f, tag, lora, x_in, qkv, Hm, Ha):
+    def _lora_fwd(self, f, tag, lora, x_in, qkv, Hm, Ha, drops):
         """One LoRA forward op behind the Q|K|V launch: qkv columns += s (x A^T) B^T for every adapter of the active streams.  -> T per adapter
-        (kept for the backward; one shared buffer per shape in a forward-only plan)."""
+        (kept for the backward; one shared buffer per shape in a forward-only plan).  drops: {(stream, column block): the problem's LoRA
+        dropout}, or empty -- then the op is the one a model without LoRA dropout builds."""
         s = self.arena.lora_scale
         assert s is not None, "the arena holds LoRA adapters but no scale: build it from a model that add_lora() prepared"
         probs, T = [], {}
@@ -190,15 +195,19 @@ class SublayerBuilders:
                                        M, Hm[m], Ha[m], r, Hm[m], 3 * Ha[m], s, 0))
         assert len(probs) <= L.LORA_MAX_PROBLEMS
         arr = self.k((L.LoraProblem * len(probs))(*probs))
-        self.emit(f, L.FN_LORA_FWD, p=(arr,), n=(len(probs),))
+        if drops:
+            self.emit(f, L.FN_LORA_FWD_DROP, p=(arr, None, self.k((L.Dropout * len(probs))(*[drops[(m, c)] for m, c, _ in lora]))), n=(len(probs),))
+        else:
+            self.emit(f, L.FN_LORA_FWD, p=(arr,), n=(len(probs),))
         return T
 
-    def _lora_bwd(self, b, lora, T, x_in, dqkv, dxn, live_in, Hm, Ha):
+    def _lora_bwd(self, b, lora, T, x_in, dqkv, dxn, live_in, Hm, Ha, drops):
         """One LoRA backward op: dA, dB of every trainable adapter (a frozen one is pruned, its range reads zero) and, where the input
         gradient is live, every adapter's share of dxn -- a frozen adapter's too: the gradient passes through it.  An adapter shared by both
-        streams takes the text rows first, then the vision rows (`accumulate`), like a shared weight in _wgrad."""
+        streams takes the text rows first, then the vision rows (`accumulate`), like a shared weight in _wgrad.  drops: what _lora_fwd took --
+        each problem replays the mask of its forward problem."""
         s = self.arena.lora_scale
-        probs, written = [], set()
+        probs, written, dr = [], set(), []
         for m, c, stem in lora:
             off = self.prune(stem + ".lora_A", stem + ".lora_B")
             if off and not live_in[m]:
@@ -210,6 +219,8 @@ class SublayerBuilders:
             probs.append(L.LoraBwdProblem(_addr(x_in[m]), _addr(A), _addr(Bw), _addr(T[(m, c)]), dqkv[m].data_ptr() + 2 * c * Ha[m], _addr(dT),
                                           _addr(dxn[m]) if live_in[m] else None, _addr(gA), _addr(gB), None,
                                           M, Hm[m], Ha[m], r, Hm[m], 3 * Ha[m], Hm[m], int(stem in written), s, 0))
+            if drops:
+                dr.append(drops[(m, c)])
             if not off:
                 written.add(stem)
         if not probs:
@@ -218,12 +229,15 @@ class SublayerBuilders:
         nbytes = L.lib.vk_lora_bwd_work_bytes(arr, len(probs))
         assert nbytes > 0, "vk_lora_bwd_work_bytes refused the problems"
         work = self.tmp("lora_work_%d" % nbytes, (nbytes,), torch.uint8)
-        self.emit(b, L.FN_LORA_BWD, p=(arr, work), n=(len(probs),))
+        if drops:
+            self.emit(b, L.FN_LORA_BWD_DROP, p=(arr, work, self.k((L.Dropout * len(dr))(*dr))), n=(len(probs),))
+        else:
+            self.emit(b, L.FN_LORA_BWD, p=(arr, work), n=(len(probs),))
 
-    def _lora_proj_fwd(self, f, tag, which, items):
+    def _lora_proj_fwd(self, f, tag, which, items, drops):
         """One whole-projection LoRA forward op (vk_lora_proj_fwd).  items: [(stream, holder name, X [M, K], Y [M, N], G or None)]; G None:
         Y += s (X A^T) B^T; G: Y = gelu(Y + ...), G = gelu'(Y + ...).  -> T per stream (kept for the backward; one shared buffer per
-        shape in a forward-only plan)."""
+        shape in a forward-only plan).  drops: {stream: the problem's LoRA dropout}, or empty: the op without a mask."""
         s = self.arena.lora_scale
         assert s is not None, "the arena holds LoRA adapters but no scale: build it from a model that add_lora() prepared"
         probs, T = [], {}
@@ -235,16 +249,19 @@ class SublayerBuilders:
             probs.append(L.LoraProjProblem(_addr(X), _addr(A), _addr(Bw), _addr(T[m]), _addr(Y), _addr(G), None, M, K, N, r, X.stride(0), Y.stride(0),
                                            G.stride(0) if G is not None else 0, s, int(G is not None)))
         arr = self.k((L.LoraProjProblem * len(probs))(*probs))
-        self.emit(f, L.FN_LORA_PROJ_FWD, p=(arr,), n=(len(probs),))
+        if drops:
+            self.emit(f, L.FN_LORA_PROJ_FWD_DROP, p=(arr, None, self.k((L.Dropout * len(probs))(*[drops[it[0]] for it in items]))), n=(len(probs),))
+        else:
+            self.emit(f, L.FN_LORA_PROJ_FWD, p=(arr,), n=(len(probs),))
         return T
 
-    def _lora_proj_bwd(self, b, items):
+    def _lora_proj_bwd(self, b, items, drops):
         """One whole-projection LoRA backward op (vk_lora_proj_bwd).  items: [(stream, holder name, X, T, dY, dX or None, R or None)]: dA, dB
         of every trainable adapter (a frozen one is pruned, its range reads zero) and, where dX is given, the adapter's share of the input
         gradient, times R -- a frozen adapter's too: the gradient passes through it.  An adapter shared by both streams takes the text rows
-        first, then the vision rows (`accumulate`)."""
+        first, then the vision rows (`accumulate`).  drops: what _lora_proj_fwd took for these adapters."""
         s = self.arena.lora_scale
-        probs, written = [], set()
+        probs, written, dr = [], set(), []
         for m, stem, X, T, dY, dX, R in items:
             off = self.prune(stem + ".lora_A", stem + ".lora_B")
             if off and dX is None:
@@ -256,6 +273,8 @@ class SublayerBuilders:
             probs.append(L.LoraProjBwdProblem(_addr(X), _addr(A), _addr(Bw), _addr(T), _addr(dY), _addr(dT), _addr(dX), _addr(gA), _addr(gB), _addr(R), None,
                                               M, K, N, r, X.stride(0), dY.stride(0), dX.stride(0) if dX is not None else 0,
                                               R.stride(0) if R is not None else 0, int(stem in written), s))
+            if drops:
+                dr.append(drops[m])
             if not off:
                 written.add(stem)
         if not probs:
@@ -264,7 +283,10 @@ class SublayerBuilders:
         nbytes = L.lib.vk_lora_proj_bwd_work_bytes(arr, len(probs))
         assert nbytes > 0, "vk_lora_proj_bwd_work_bytes refused the problems"
         work = self.tmp("lora_work_%d" % nbytes, (nbytes,), torch.uint8)
-        self.emit(b, L.FN_LORA_PROJ_BWD, p=(arr, work), n=(len(probs),))
+        if drops:
+            self.emit(b, L.FN_LORA_PROJ_BWD_DROP, p=(arr, work, self.k((L.Dropout * len(dr))(*dr))), n=(len(probs),))
+        else:
+            self.emit(b, L.FN_LORA_PROJ_BWD, p=(arr, work), n=(len(probs),))
 
     def _tail_fwd(self, tag, ms, names, d, x_in, Hm):
         """The tail both kinds of sub-layer end in: y = LayerNorm(dropout(d) + x_in) per active stream, d = the output projection's result (the
@@ -332,6 +354,9 @@ class SublayerBuilders:
         if (lora_up or lora_dn) and self.fp8:
             raise NotImplementedError("feed-forward sub-layer %d has LoRA adapters: the fp8 (e4m3) projection path does not run them; "
                                       "merge_lora() first or use the bf16 projections" % n)
+        # LoRA dropout: a site per problem, handed out stream by stream, within a stream up, then down; empty without a rate
+        ld = self.lora_drops([(m, which) for m in ms for which, have in (("up", lora_up), ("dn", lora_dn)) if m in have])
+        ld_of = lambda which, have: {m: ld[(m, which)] for m in have if ld}
         if self.fp8:
             # the GELU output also leaves the epilogue as e4m3 with one static scale (the FFN-down projection's A operand), de-quantised
             # there through scale_a = 1 / multiplier
@@ -359,10 +384,10 @@ class SublayerBuilders:
                     self.gemm(f, L.NT, L.EPI_GELU, rest)
                 self.gemm(f, L.NT, L.EPI_BF16, [self.prob(x_in[m], self.W(names[m]["up"] + ".weight"), h[m], self.st[m].M, Im[m], Hm[m], Hm[m], Hm[m], Im[m],
                                                           bias=self.Pm(names[m]["up"] + ".bias")) for m in ms if m in lora_up])
-                Tup = self._lora_proj_fwd(f, tag, "up", [(m, lora_up[m], x_in[m], h[m], gp[m]) for m in ms if m in lora_up])
+                Tup = self._lora_proj_fwd(f, tag, "up", [(m, lora_up[m], x_in[m], h[m], gp[m]) for m in ms if m in lora_up], ld_of("up", lora_up))
             self.gemm(f, L.NT, L.EPI_BF16, down)
             if lora_dn:
-                Tdn = self._lora_proj_fwd(f, tag, "dn", [(m, lora_dn[m], h[m], d[m], None) for m in ms if m in lora_dn])
+                Tdn = self._lora_proj_fwd(f, tag, "dn", [(m, lora_dn[m], h[m], d[m], None) for m in ms if m in lora_dn], ld_of("dn", lora_dn))
         tail = self._tail_fwd(tag, ms, names, d, x_in, Hm)
         if self.fwd_only:
             return []
@@ -392,7 +417,7 @@ class SublayerBuilders:
         keep_d1 = {m: m in ma and (live_in[m] or not self.fz(*of(m, "up")) or ad_on(lora_up, m)) for m in ms}
         self.gemm_kept(b, L.NN, L.EPI_MULR, d1, [keep_d1[m] for m in ms])
         if lora_dn:      # directly behind d1, in front of the weight-gradient side block and d2: both read the du this op adds to, through gelu'
-            self._lora_proj_bwd(b, [(m, lora_dn[m], h[m], Tdn[m], dd[m], du[m] if keep_d1[m] else None, gp[m]) for m in ma if m in lora_dn])
+            self._lora_proj_bwd(b, [(m, lora_dn[m], h[m], Tdn[m], dd[m], du[m] if keep_d1[m] else None, gp[m]) for m in ma if m in lora_dn], ld_of("dn", lora_dn))
         # The weight gradients need dd, h, du and x_in: everything but the LAST dgrad's output.  Their side-stream block is listed in front of that
         # dgrad, so that it starts beside a GEMM (two MFMA-bound launches share the chip without loss) instead of beside the LayerNorm backward
         # that follows, which it used to keep waiting for CUs (profiles/r03_experiments.md: 17.00 / 16.94 -> 16.52 / 16.54 ms per step).
@@ -404,7 +429,8 @@ class SublayerBuilders:
             for m in ma:
                 if m in lora_up and not keep_d1[m]:      # no du: the adapter is frozen and nothing upstream is trainable
                     assert self.prune(*leaves(lora_up[m]))
-            self._lora_proj_bwd(b, [(m, lora_up[m], x_in[m], Tup[m], du[m], dxn[m] if live_in[m] else None, None) for m in ma if m in lora_up and keep_d1[m]])
+            self._lora_proj_bwd(b, [(m, lora_up[m], x_in[m], Tup[m], du[m], dxn[m] if live_in[m] else None, None) for m in ma if m in lora_up and keep_d1[m]],
+                                ld_of("up", lora_up))
         return b
 
     def _wgrad(self, b, ms, shared, specs, blocks=None, dead=()):

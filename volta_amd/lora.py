@@ -2,15 +2,17 @@
 sub-layer, the up and down projections of a feed-forward sub-layer.
 
     from volta_amd.lora import add_lora, mark_only_lora_trainable
-    add_lora(model, r=8, alpha=16, targets=("query", "value"))
+    add_lora(model, r=8, alpha=16, targets=("query", "value"), dropout=0.1)
     mark_only_lora_trainable(model, also=("clfs_dict.",))
 
 An adapter is two ordinary parameters on the `LinearParams` holder of a projection, `lora_A` [r, in] and `lora_B` [out, r]; the engine adds
 `(alpha / r) * (x A^T) B^T` to that projection's columns of the fused Q|K|V product with the kernels of csrc/lora.hip and returns both
 parameters' gradients through the gradient arena, like any other weight's ("Low-rank adapters").  The targets
 `attn_out` (attention_output.dense), `ffn_up` (intermediate.dense) and `ffn_down` (output.dense) run on the vk_lora_proj_* entry points:
-the FFN-up adapter's term enters inside the GELU, the FFN-down adapter's input gradient passes through gelu'.  There is no LoRA
-dropout and one rank per model; the e4m3 projection path refuses a model with adapters."""
+the FFN-up adapter's term enters inside the GELU, the FFN-down adapter's input gradient passes through gelu'.  `dropout` is LoRA
+dropout: in train mode the adapter (not the base projection) reads `keep * x / (1 - p)`, a Philox mask of its own per adapter and stream
+made inside the kernels (vk_lora_*_drop) and replayed by the backward; eval mode and the retrieval scorer run without it.  One rank and
+one rate per model; the e4m3 projection path refuses a model with adapters."""
 import math
 
 import torch
@@ -64,9 +66,17 @@ def _adapted(root):
     return [(name, h) for name, h in _holders(root) if "lora_A" in h._parameters]
 
 
-def add_lora(model, r=8, alpha=16, targets=("query", "value"), modalities=("text", "vision"), sublayers=None, seed=0):
+def _rate(dropout):
+    p = float(dropout)
+    if not 0.0 <= p < 1.0:          # NaN fails both comparisons
+        raise ValueError("LoRA dropout %r: 0 <= p < 1" % (dropout,))
+    return p
+
+
+def add_lora(model, r=8, alpha=16, targets=("query", "value"), modalities=("text", "vision"), sublayers=None, seed=0, dropout=0.0):
     """Adds `lora_A` [r, in] (uniform in +-1 / sqrt(in), drawn on the CPU from torch.Generator().manual_seed(seed)) and `lora_B` [out, r]
-    (zero) to every targeted projection; returns the new parameters' names.  Call it before the optimizer is built."""
+    (zero) to every targeted projection; returns the new parameters' names.  Call it before the optimizer is built.  dropout: the rate of
+    the dropout on the adapters' input in train mode (set_lora_dropout changes it later); `lora_config` lists it only when it is > 0."""
     root = _root(model)
     targets, modalities = tuple(targets), tuple(modalities)
     if r not in RANKS:
@@ -77,6 +87,7 @@ def add_lora(model, r=8, alpha=16, targets=("query", "value"), modalities=("text
         raise ValueError("LoRA modalities %r: 'text' and / or 'vision'" % (modalities,))
     if not alpha > 0:
         raise ValueError("LoRA alpha %r must be positive" % (alpha,))
+    p = _rate(dropout)
     if getattr(root, "lora_config", None) is not None or _adapted(root):
         raise RuntimeError("the model already has LoRA adapters (one rank and scale per model): merge_lora() or remove_lora() first")
     kinds = {_PLACE[t][0] for t in targets}
@@ -101,8 +112,28 @@ def add_lora(model, r=8, alpha=16, targets=("query", "value"), modalities=("text
             names.append("%s.%s" % (name, leaf))
     root.lora_config = dict(r=int(r), alpha=float(alpha), targets=list(targets), modalities=list(modalities),
                             sublayers=list(hosts if sublayers is None else sublayers))
+    if p > 0.0:
+        root.lora_config["dropout"] = p
     root._invalidate_engine()
     return names
+
+
+def set_lora_dropout(model, p):
+    """Changes the LoRA dropout rate of a model that has adapters (0 switches it off).  The cached plans go, the parameter arena stays."""
+    root = _root(model)
+    if getattr(root, "lora_config", None) is None:
+        raise RuntimeError("the model has no LoRA adapters: add_lora() first")
+    p = _rate(p)
+    root.lora_config.pop("dropout", None)
+    if p > 0.0:
+        root.lora_config["dropout"] = p
+    if root.__dict__.get("_engines"):
+        root.__dict__["_engines"] = {}
+
+
+def lora_dropout(model):
+    cfg = getattr(_root(model), "lora_config", None)
+    return 0.0 if cfg is None else cfg.get("dropout", 0.0)
 
 
 def lora_scale(model):

@@ -182,7 +182,7 @@ class EngineHostModel(PreTrainedModel):
     _heads_mode = "pretrain"           # StepEngine(heads=...)
     _torch_param_prefixes = ()         # parameters of torch-side head modules: autograd, not the engine, writes their gradients
     task_cfg = None
-    lora_config = None                 # volta_amd.lora.add_lora: dict(r, alpha, targets, modalities, sublayers) while the model has adapters
+    lora_config = None                 # volta_amd.lora.add_lora: dict(r, alpha, targets, modalities, sublayers[, dropout]) while the model has adapters
     # `_vk_is_model` lets clip_grad_norm_(model.parameters()) recognise the whole arena without walking it: on the instance, a nested model is none
     _ROOT_STATE = dict(_vk_is_model=True, _arena=None, _engines=None, _step=0, _seed_base=None, _last=None, _ddp=None, _fwd_serial=0,
                        _fp8=False, _task_dropout=0.1)
@@ -257,7 +257,7 @@ class EngineHostModel(PreTrainedModel):
                 del self._engines[k]
             task = (task_id, self.task_cfg[task_id]) if task_id is not None else None
             eng = StepEngine(self.config, arena, B, T, Rv, train, heads=self._heads_mode, fp8=self._fp8, task=task,
-                             task_dropout=self._task_dropout, attn_maps=maps, frozen=frozen)
+                             task_dropout=self._task_dropout, attn_maps=maps, frozen=frozen, lora_dropout=(self.lora_config or {}).get("dropout", 0.0))
             self._engines[key] = eng
         return eng
 

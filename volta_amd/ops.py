@@ -584,3 +584,46 @@ def lora_proj_bwd(problems, work=None):
     assert work.numel() * work.element_size() >= need and work.data_ptr() % 16 == 0
     check(L.lib.vk_lora_proj_bwd(arr, len(problems), ptr(work), stream_ptr()))
     return work
+
+
+# ---- LoRA dropout (vk_lora_*_drop): the calls above with one dropout entry per problem, a keep mask on the adapter's input
+def lora_drop(seed, site, p):
+    """The vk_dropout of one problem: `seed` a device int64 [1] tensor (None with p = 0), `site` the problem's own site, p the rate."""
+    return L.dropout_cfg(ptr(seed), int(site), float(p))
+
+
+def _drop_array(problems, drops):
+    assert len(drops) == len(problems), "one dropout entry per problem"
+    return (L.Dropout * len(drops))(*drops)
+
+
+def lora_fwd_drop(problems, drops):
+    arr = (L.LoraProblem * len(problems))(*problems)
+    check(L.lib.vk_lora_fwd_drop(arr, _drop_array(problems, drops), len(problems), stream_ptr()))
+
+
+def lora_bwd_drop(problems, drops, work=None):
+    arr = (L.LoraBwdProblem * len(problems))(*problems)
+    need = L.lib.vk_lora_bwd_work_bytes(arr, len(problems))
+    assert need > 0, "vk_lora_bwd_work_bytes refused the problems"
+    if work is None:
+        work = torch.empty(need, dtype=torch.uint8, device="cuda")
+    assert work.numel() * work.element_size() >= need and work.data_ptr() % 16 == 0
+    check(L.lib.vk_lora_bwd_drop(arr, _drop_array(problems, drops), len(problems), ptr(work), stream_ptr()))
+    return work
+
+
+def lora_proj_fwd_drop(problems, drops):
+    arr = (L.LoraProjProblem * len(problems))(*problems)
+    check(L.lib.vk_lora_proj_fwd_drop(arr, _drop_array(problems, drops), len(problems), stream_ptr()))
+
+
+def lora_proj_bwd_drop(problems, drops, work=None):
+    arr = (L.LoraProjBwdProblem * len(problems))(*problems)
+    need = L.lib.vk_lora_proj_bwd_work_bytes(arr, len(problems))
+    assert need > 0, "vk_lora_proj_bwd_work_bytes refused the problems"
+    if work is None:
+        work = torch.empty(need, dtype=torch.uint8, device="cuda")
+    assert work.numel() * work.element_size() >= need and work.data_ptr() % 16 == 0
+    check(L.lib.vk_lora_proj_bwd_drop(arr, _drop_array(problems, drops), len(problems), ptr(work), stream_ptr()))
+    return work
