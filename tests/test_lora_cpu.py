@@ -342,3 +342,66 @@ def test_fp8_refuses_adapters(matrix):
     eng = StepEngine(model.config, arena, B, T, Rv, False, heads="score", part="pair", split=split_plan(model.config), projection_dtype="bf16")
     from volta_amd import _lib as L
     assert len(lora_ops(eng.fwd, L.FN_LORA_FWD)) == 2 and not eng.bwd.ops
+
+
+# ---------------------------------------------------------------------------------------------- the C ABI
+def test_qkv_host_refusals_without_gpu():
+    """vk_lora_fwd / vk_lora_bwd refuse on the host before any launch, under their own names and with their own cap (K, N <= 1024: the
+    row product stages a whole panel in LDS).  Host addresses, no device: every call here must come back refused."""
+    import ctypes
+    from volta_amd import _lib as L
+    err = lambda: L.lib.vk_last_error().decode()
+    buf = (ctypes.c_char * 8192)()
+    a = (ctypes.addressof(buf) + 15) & ~15
+    T, Y, dT, dX, dA, dB = a + 512, a + 1024, a + 1536, a + 2048, a + 3072, a + 4096
+
+    def fwd_p(**kw):
+        f = dict(X=a, A=a, B=a, T=T, Y=Y, dyn=None, M=4, K=64, N=64, r=4, ldx=64, ldy=64, scale=1.0, reserved_=0)
+        f.update(kw)
+        return L.LoraProblem(**f)
+
+    def bwd_p(**kw):
+        f = dict(X=a, A=a, B=a, T=T, dY=Y, dT=dT, dX=dX, dA=dA, dB=dB, dyn=None, M=4, K=64, N=64, r=4, ldx=64, ldy=64, lddx=64, accumulate=0,
+                 scale=1.0, reserved_=0)
+        f.update(kw)
+        return L.LoraBwdProblem(**f)
+
+    def fwd(*ps, n=None):
+        assert L.lib.vk_lora_fwd((L.LoraProblem * max(len(ps), 1))(*ps), len(ps) if n is None else n, None) != 0
+        assert err().startswith("vk_lora_fwd: "), err()
+        return err()
+
+    def bwd(*ps, n=None, work=a):
+        assert L.lib.vk_lora_bwd((L.LoraBwdProblem * max(len(ps), 1))(*ps), len(ps) if n is None else n, work, None) != 0
+        assert err().startswith("vk_lora_bwd: "), err()
+        return err()
+
+    for call, prob, y in ((fwd, fwd_p, "Y"), (bwd, bwd_p, "dY")):
+        # the cap of these entry points, whatever the whole-projection ones take
+        assert "K = 1088, N = 64 (multiples of 64, at most 1024)" in call(prob(K=1088, ldx=1088))
+        assert "K = 64, N = 1088 (multiples of 64, at most 1024)" in call(prob(N=1088, ldy=1088))
+        assert "K = 96, N = 64 (multiples of 64, at most 1024)" in call(prob(K=96, ldx=96))
+        assert "problem 0: r = 12 (4, 8, 16 or 32)" in call(prob(r=12))
+        assert "problem 0: NULL operand 2" in call(prob(B=None))
+        assert "problem 0: operand 4 is not 16-byte aligned" in call(prob(**{y: Y + 2}))
+        assert "problem 0: leading dimensions 56 / 64" in call(prob(ldx=56))
+        assert "problem 1: r = 8, problem 0 has 4 (one rank per call)" in call(prob(), prob(r=8, T=T + 64, Y=Y + 256) if call is fwd else prob(r=8, dT=dT + 64))
+        assert "0 problems (1 .. 6)" in call(prob(), n=0)
+        assert "7 problems (1 .. 6)" in call(prob(), n=7)
+    assert "problems 0 and 1 write the same T or Y" in fwd(fwd_p(), fwd_p(Y=Y + 256))
+    assert "problems 0 and 1 write the same T or Y" in fwd(fwd_p(), fwd_p(T=T + 64))
+    assert "problems 0 and 1 write the same dT" in bwd(bwd_p(), bwd_p(dA=dA + 512, dB=dB + 512))
+    assert "problem 0: dA and dB are both set" in bwd(bwd_p(dB=None))
+    assert "problem 0: dA and dB are both set" in bwd(bwd_p(dA=dA + 4))
+    assert "problem 0 has no output" in bwd(bwd_p(dA=None, dB=None, dX=None))
+    assert "problem 0: dX alignment / lddx 56" in bwd(bwd_p(lddx=56))
+    assert "problem 1 writes the gradients of an earlier problem without `accumulate`" in bwd(bwd_p(), bwd_p(dT=dT + 64))
+    assert "problem 1: a shared adapter has one dA, one dB" in bwd(bwd_p(), bwd_p(dT=dT + 64, dA=dA + 512, accumulate=1))
+    assert "problem 1: the (at most 3) adapters that add into one dX share its shape" in bwd(bwd_p(), bwd_p(dT=dT + 64, dA=dA + 512, dB=dB + 512, M=3))
+    assert "dA of problem 1 is dB of problem 0" in bwd(bwd_p(), bwd_p(dT=dT + 64, dA=dB, dB=dA + 512, dX=None))
+    assert "workspace must be a 16-byte aligned buffer of vk_lora_bwd_work_bytes()" in bwd(bwd_p(), work=None)
+    assert "workspace must be a 16-byte aligned buffer of vk_lora_bwd_work_bytes()" in bwd(bwd_p(), work=a + 8)
+    one = (L.LoraBwdProblem * 1)(bwd_p())
+    assert L.lib.vk_lora_bwd_work_bytes(one, 0) < 0 and L.lib.vk_lora_bwd_work_bytes(one, 7) < 0 and L.lib.vk_lora_bwd_work_bytes(None, 1) < 0
+    assert L.lib.vk_lora_bwd_work_bytes((L.LoraBwdProblem * 1)(bwd_p(K=0)), 1) < 0
+    assert L.lib.vk_lora_bwd_work_bytes(one, 1) == 256 * ((4 * (64 + 64) * 4 + 255) // 256)          # one row block: r (K + N) floats

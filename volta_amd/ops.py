@@ -453,21 +453,44 @@ def _extent(t):
     return t.untyped_storage().nbytes() // t.element_size() - t.storage_offset()
 
 
-def _lora_common(X, A, B, T, Y, M, what):
+def _lora_common(X, A, B, T, Y, M, what, cap=1024, y="a [M, N] column range"):
     r, K = A.shape
     N = B.shape[0]
     assert r in (4, 8, 16, 32) and tuple(B.shape) == (N, r), "A [r, K] and B [N, r] with r in 4, 8, 16, 32"
-    assert K % 64 == 0 and N % 64 == 0 and K <= 1024 and N <= 1024, "K and N: multiples of 64, at most 1024"
+    assert K % 64 == 0 and N % 64 == 0 and K <= cap and N <= cap, "K and N: multiples of 64, at most %d" % cap
     for t in (X, A, B, T, Y):
         _bf16(t)
         assert t.data_ptr() % 16 == 0, "16-byte alignment required"
     assert A.is_contiguous() and B.is_contiguous() and T.is_contiguous(), "A, B and T are dense"
     ldx, ldy = X.stride(0), Y.stride(0)
     assert X.stride(1) == 1 and Y.stride(1) == 1 and ldx % 8 == 0 and ldy % 8 == 0 and ldx >= K and ldy >= N
-    assert X.shape[1] == K and Y.shape[1] == N, "%s: X [M, K] and a [M, N] column range" % what
+    assert X.shape[1] == K and Y.shape[1] == N, "%s: X [M, K] and %s" % (what, y)
     assert M <= X.shape[0] and M <= Y.shape[0] and (M == 0 or ((M - 1) * ldx + K <= _extent(X) and (M - 1) * ldy + N <= _extent(Y)))
     assert T.numel() >= M * r
     return r, K, N, ldx, ldy
+
+
+def _lora_work(work_bytes, arr, n, work, device="cuda"):
+    """The workspace of a backward call: `work`, or a new buffer, of at least what `work_bytes` asks for these problems."""
+    need = getattr(L.lib, work_bytes)(arr, n)
+    assert need > 0, work_bytes + " refused the problems"
+    if work is None:
+        work = torch.empty(need, dtype=torch.uint8, device=device)
+    assert work.numel() * work.element_size() >= need and work.data_ptr() % 16 == 0
+    return work
+
+
+def _lora_run(fn, cls, problems, drops=None, work_bytes=None, work=None):
+    """One vk_lora_* call: the problem array, a _drop call's dropout array, a backward call's workspace (which it returns)."""
+    n = len(problems)
+    arr = (cls * n)(*problems)
+    args = [arr] if drops is None else [arr, _drop_array(problems, drops)]
+    if work_bytes is not None:
+        work = _lora_work(work_bytes, arr, n, work)
+        check(getattr(L.lib, fn)(*args, n, ptr(work), stream_ptr()))
+    else:
+        check(getattr(L.lib, fn)(*args, n, stream_ptr()))
+    return work
 
 
 def lora_problem(X, A, B, T, Y, scale, M=None, dyn=None):
@@ -496,46 +519,18 @@ def lora_bwd_problem(X, A, B, T, dY, dT, dX, dA, dB, scale, M=None, accumulate=F
 
 
 def lora_fwd(problems):
-    arr = (L.LoraProblem * len(problems))(*problems)
-    check(L.lib.vk_lora_fwd(arr, len(problems), stream_ptr()))
+    _lora_run("vk_lora_fwd", L.LoraProblem, problems)
 
 
 def lora_bwd_work(problems, device):
-    arr = (L.LoraBwdProblem * len(problems))(*problems)
-    nbytes = L.lib.vk_lora_bwd_work_bytes(arr, len(problems))
-    assert nbytes > 0, "vk_lora_bwd_work_bytes refused the problems"
-    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+    return _lora_work("vk_lora_bwd_work_bytes", (L.LoraBwdProblem * len(problems))(*problems), len(problems), None, device)
 
 
 def lora_bwd(problems, work=None):
-    arr = (L.LoraBwdProblem * len(problems))(*problems)
-    need = L.lib.vk_lora_bwd_work_bytes(arr, len(problems))
-    assert need > 0, "vk_lora_bwd_work_bytes refused the problems"
-    if work is None:
-        work = torch.empty(need, dtype=torch.uint8, device="cuda")
-    assert work.numel() * work.element_size() >= need and work.data_ptr() % 16 == 0
-    check(L.lib.vk_lora_bwd(arr, len(problems), ptr(work), stream_ptr()))
-    return work
+    return _lora_run("vk_lora_bwd", L.LoraBwdProblem, problems, work_bytes="vk_lora_bwd_work_bytes", work=work)
 
 
 # ---- adapters on a whole projection (vk_lora_proj_*): K and N up to 4096, the GELU in the forward, a saved gelu' in the input gradient
-def _lora_proj_common(X, A, B, T, Y, M, what):
-    r, K = A.shape
-    N = B.shape[0]
-    assert r in (4, 8, 16, 32) and tuple(B.shape) == (N, r), "A [r, K] and B [N, r] with r in 4, 8, 16, 32"
-    assert K % 64 == 0 and N % 64 == 0 and K <= 4096 and N <= 4096, "K and N: multiples of 64, at most 4096"
-    for t in (X, A, B, T, Y):
-        _bf16(t)
-        assert t.data_ptr() % 16 == 0, "16-byte alignment required"
-    assert A.is_contiguous() and B.is_contiguous() and T.is_contiguous(), "A, B and T are dense"
-    ldx, ldy = X.stride(0), Y.stride(0)
-    assert X.stride(1) == 1 and Y.stride(1) == 1 and ldx % 8 == 0 and ldy % 8 == 0 and ldx >= K and ldy >= N
-    assert X.shape[1] == K and Y.shape[1] == N, "%s: X [M, K] and Y [M, N]" % what
-    assert M <= X.shape[0] and M <= Y.shape[0] and (M == 0 or ((M - 1) * ldx + K <= _extent(X) and (M - 1) * ldy + N <= _extent(Y)))
-    assert T.numel() >= M * r
-    return r, K, N, ldx, ldy
-
-
 def _lora_side(t, M, cols, what):
     """A bf16 [M, cols] operand beside X or Y (G, R, dX) -> its leading dimension."""
     _bf16(t)
@@ -548,7 +543,7 @@ def _lora_side(t, M, cols, what):
 def lora_proj_problem(X, A, B, T, Y, scale, G=None, M=None, dyn=None):
     """One vk_lora_proj_problem.  G None: Y += s (X A^T) B^T; G [M, N]: Y = gelu(Y + ...), G = gelu'(Y + ...)."""
     M = X.shape[0] if M is None else M
-    r, K, N, ldx, ldy = _lora_proj_common(X, A, B, T, Y, M, "lora_proj_problem")
+    r, K, N, ldx, ldy = _lora_common(X, A, B, T, Y, M, "lora_proj_problem", 4096, "Y [M, N]")
     ldg = 0 if G is None else _lora_side(G, M, N, "G")
     return L.LoraProjProblem(ptr(X), ptr(A), ptr(B), ptr(T), ptr(Y), ptr(G), ptr(dyn), M, K, N, r, ldx, ldy, ldg, float(scale), int(G is not None))
 
@@ -557,7 +552,7 @@ def lora_proj_bwd_problem(X, A, B, T, dY, dT, dX, dA, dB, scale, R=None, M=None,
     """One vk_lora_proj_bwd_problem; dX None: the input gradient is not live; dA and dB None: a frozen adapter; R: the gelu' buffer of the
     GEMM that produced X, multiplied into the adapter's share of dX."""
     M = X.shape[0] if M is None else M
-    r, K, N, ldx, ldy = _lora_proj_common(X, A, B, T, dY, M, "lora_proj_bwd_problem")
+    r, K, N, ldx, ldy = _lora_common(X, A, B, T, dY, M, "lora_proj_bwd_problem", 4096, "Y [M, N]")
     _bf16(dT)
     assert dT.is_contiguous() and dT.numel() >= M * r and dT.data_ptr() % 16 == 0
     assert (dA is None) == (dB is None), "dA and dB: both or neither"
@@ -571,19 +566,11 @@ def lora_proj_bwd_problem(X, A, B, T, dY, dT, dX, dA, dB, scale, R=None, M=None,
 
 
 def lora_proj_fwd(problems):
-    arr = (L.LoraProjProblem * len(problems))(*problems)
-    check(L.lib.vk_lora_proj_fwd(arr, len(problems), stream_ptr()))
+    _lora_run("vk_lora_proj_fwd", L.LoraProjProblem, problems)
 
 
 def lora_proj_bwd(problems, work=None):
-    arr = (L.LoraProjBwdProblem * len(problems))(*problems)
-    need = L.lib.vk_lora_proj_bwd_work_bytes(arr, len(problems))
-    assert need > 0, "vk_lora_proj_bwd_work_bytes refused the problems"
-    if work is None:
-        work = torch.empty(need, dtype=torch.uint8, device="cuda")
-    assert work.numel() * work.element_size() >= need and work.data_ptr() % 16 == 0
-    check(L.lib.vk_lora_proj_bwd(arr, len(problems), ptr(work), stream_ptr()))
-    return work
+    return _lora_run("vk_lora_proj_bwd", L.LoraProjBwdProblem, problems, work_bytes="vk_lora_proj_bwd_work_bytes", work=work)
 
 
 # ---- LoRA dropout (vk_lora_*_drop): the calls above with one dropout entry per problem, a keep mask on the adapter's input
@@ -598,32 +585,16 @@ def _drop_array(problems, drops):
 
 
 def lora_fwd_drop(problems, drops):
-    arr = (L.LoraProblem * len(problems))(*problems)
-    check(L.lib.vk_lora_fwd_drop(arr, _drop_array(problems, drops), len(problems), stream_ptr()))
+    _lora_run("vk_lora_fwd_drop", L.LoraProblem, problems, drops)
 
 
 def lora_bwd_drop(problems, drops, work=None):
-    arr = (L.LoraBwdProblem * len(problems))(*problems)
-    need = L.lib.vk_lora_bwd_work_bytes(arr, len(problems))
-    assert need > 0, "vk_lora_bwd_work_bytes refused the problems"
-    if work is None:
-        work = torch.empty(need, dtype=torch.uint8, device="cuda")
-    assert work.numel() * work.element_size() >= need and work.data_ptr() % 16 == 0
-    check(L.lib.vk_lora_bwd_drop(arr, _drop_array(problems, drops), len(problems), ptr(work), stream_ptr()))
-    return work
+    return _lora_run("vk_lora_bwd_drop", L.LoraBwdProblem, problems, drops, "vk_lora_bwd_work_bytes", work)
 
 
 def lora_proj_fwd_drop(problems, drops):
-    arr = (L.LoraProjProblem * len(problems))(*problems)
-    check(L.lib.vk_lora_proj_fwd_drop(arr, _drop_array(problems, drops), len(problems), stream_ptr()))
+    _lora_run("vk_lora_proj_fwd_drop", L.LoraProjProblem, problems, drops)
 
 
 def lora_proj_bwd_drop(problems, drops, work=None):
-    arr = (L.LoraProjBwdProblem * len(problems))(*problems)
-    need = L.lib.vk_lora_proj_bwd_work_bytes(arr, len(problems))
-    assert need > 0, "vk_lora_proj_bwd_work_bytes refused the problems"
-    if work is None:
-        work = torch.empty(need, dtype=torch.uint8, device="cuda")
-    assert work.numel() * work.element_size() >= need and work.data_ptr() % 16 == 0
-    check(L.lib.vk_lora_proj_bwd_drop(arr, _drop_array(problems, drops), len(problems), ptr(work), stream_ptr()))
-    return work
+    return _lora_run("vk_lora_proj_bwd_drop", L.LoraProjBwdProblem, problems, drops, "vk_lora_proj_bwd_work_bytes", work)
