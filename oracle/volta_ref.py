@@ -976,7 +976,7 @@ def tasks_forward(sd, cfg, task_cfg, task_id, input_ids, image_feat, image_loc, 
 # The reference draws from Python's `random` / numpy; here every decision is a function of an explicit 32-bit word per
 # (pair, slot, stream) so that the policy can be replayed: the product's HIP kernels take the words from Philox
 # (stream = site, counter = (slot, pair, site, 0)), the fixtures feed the reference code the same words as word / 2^32.
-CC_T15 = int(0.15 * 2 ** 32)            # "prob < 0.15"
+CC_T15 = 644245095                      # "prob < 0.15": word / 2^32 < 0.15 in double <=> word < 644245095 (0.15 * 2^32 = 644245094.4)
 CC_SITE_TOKEN, CC_SITE_RANDTOK, CC_SITE_REGION, CC_SITE_CAPTION = 0, 1, 2, 3
 
 

@@ -13,7 +13,7 @@
 
 namespace vk {
 
-constexpr uint32_t CC_T15 = 644245094u;      // floor(0.15 * 2^32): "prob < 0.15"
+constexpr uint32_t CC_T15 = 644245095u;      // "prob < 0.15": word / 2^32 < 0.15 in double <=> word < 644245095 (0.15 * 2^32 = 644245094.4)
 __device__ __forceinline__ uint32_t cc_word(uint64_t seed, uint32_t stream, uint32_t pair, uint32_t slot) {
     return philox4_rounds<10>(slot, pair, stream, 0u, (uint32_t)seed, (uint32_t)(seed >> 32))[0];
 }
@@ -27,11 +27,17 @@ __device__ __forceinline__ bool cc_swap(const vk_concap_args& a, int b, int& cap
     }
     return false;
 }
+// every fp32 operation rounds on its own, as numpy's does in the reference (iou :31-68): a product fused into the area sum or into the
+// subtraction of the intersection moves the quotient by an ulp, and with it the `> 0.4` decision and the global-feature divisor.
+// Plain operators under the pragma, not __fmul_rn / __fadd_rn: this toolchain defines those as `x * y` / `x + y` in a header the pragma does
+// not reach (__clang_hip_math.h), and they contract like any other product and sum.
 __device__ __forceinline__ float cc_iou(const float* bi, const float* bj) {
+#pragma clang fp contract(off)
     const float ai = (bi[2] - bi[0] + 1.f) * (bi[3] - bi[1] + 1.f), aj = (bj[2] - bj[0] + 1.f) * (bj[3] - bj[1] + 1.f);
     float iw = fminf(bi[2], bj[2]) - fmaxf(bi[0], bj[0]) + 1.f, ih = fminf(bi[3], bj[3]) - fmaxf(bi[1], bj[1]) + 1.f;
     iw = fmaxf(iw, 0.f); ih = fmaxf(ih, 0.f);
-    return iw * ih / (ai + aj - iw * ih);
+    const float inter = iw * ih;
+    return inter / (ai + aj - inter);
 }
 
 // region decisions of pair b into LDS: sel[r] (label 1), zero[r] (feature row zeroed), returns the global-feature divisor
