@@ -598,6 +598,87 @@ int vk_radam_step(const vk_radam_args* a, vk_stream_t s);
 /* The same element function over `n` device descriptors of fp32 tensors OUTSIDE the arena (a torch head on a standalone BertModel) in ONE
  * launch; descriptor cls selects the class.  a->p / g / m / v / shadow / chunk_class / n are ignored; max_numel sizes the grid. */
 int vk_radam_step_list(const vk_radam_args* a, const vk_adamw_tensor* list, int n, int64_t max_numel, vk_stream_t s);
+/* Fused LAMB (volta_amd/csrc/lamb.hip) with the semantics of apex.optimizers.FusedLAMB as the reference tree vendors it
+ * (apex/apex/optimizers/fused_lamb.py, apex/csrc/multi_tensor_lamb.cu): Adam moments, then a trust ratio PER PARAMETER TENSOR.  Tensor
+ * boundaries fall inside the arena's 1024-element chunks (the three biases of a fused Q|K|V slot share one), so the work is described by
+ * tables instead of chunk classes:
+ *   tensors  one vk_lamb_tensor per tensor stepped this call, arena views and tensors outside the arena alike; tensors of one norm group
+ *            are consecutive and the groups ascend
+ *   pieces   one vk_lamb_piece per workgroup: `count` <= VK_LAMB_PIECE elements of tensor `tensor` from element `offset` on; the pieces
+ *            of a tensor are consecutive (piece0 .. piece0 + npieces), in offset order, and tile it exactly once
+ *   groups   one vk_lamb_group per norm group: its range of pieces and its max_grad_norm
+ * Per element of tensor t, with k = t.cls, n = t.group, every operation in fp32 unless it says double:
+ *   gs   = grad_scale * clip[1]                         (clip NULL: grad_scale)
+ *   S_n  = sum of g^2 over the pieces of group n: a piece's sum is a float, the pieces' sums are added in double in a fixed order;
+ *          with VK_LAMB_GLOBAL_NORM every group takes S = S_0 + S_1 + ... (group order, double) instead
+ *   norm = (float)sqrt(S_n) * |gs|                       the norm of the gradient the step consumes
+ *   c_n  = norm / max_grad_norm_n  when max_grad_norm_n > 0 and norm > max_grad_norm_n, else 1     (max_grad_norm <= 0: no clipping)
+ *   g'   = (g * gs) / c_n ;  without VK_LAMB_ADAM_W_MODE and wd_k != 0:  g' = g' + wd_k p
+ *   m    = b1 m + b3 g' ;  v = b2 v + (1 - b2) g'^2          b3 = 1 - b1 with VK_LAMB_GRAD_AVERAGING, else 1
+ *   u    = (m / bc1_k) / (sqrt(v / bc2_k) + eps) ;  with VK_LAMB_ADAM_W_MODE and wd_k != 0:  u = u + wd_k p
+ *   P_t  = sum of p^2, U_t = sum of u^2 over tensor t (p BEFORE the update): per piece in fp32, the pieces' sums in double in a fixed order
+ *   ratio_t = lr_k * (|p_t| / |u_t|)  when |p_t| = (float)sqrt(P_t) and |u_t| = (float)sqrt(U_t) are both non-zero, else lr_k
+ *   p    = p - ratio_t u ;  shadow = bf16(p) round to nearest even (where t.shadow is not NULL)
+ * bc1_k / bc2_k are the host's 1 - beta^step of the class (1 without bias correction).  m and v are written by the first stage; the second
+ * recomputes u from the m, v and p it reads with the same element function (the same bits), so there is no update buffer and g is only
+ * read.  No floating-point atomics: equal inputs give equal bits, and P_t, U_t, ratio_t are functions of tensor t's data alone.
+ * table[4 t .. 4 t + 3] = {ratio_t, ratio_t / lr_k as |p_t| / |u_t| or 1, |p_t|, |u_t|}.  Six launches whatever the number of tensors
+ * (three when no group clips).  Refused before anything is launched (-1, vk_last_error): a NULL or not 4-byte aligned p / g / m / v, a
+ * shadow not 2-byte aligned, a negative numel, a class outside 0 .. VK_LAMB_CLASSES - 1, a group outside 0 .. ngroups - 1, a piece with
+ * count < 1 or > VK_LAMB_PIECE, one past its tensor's end, pieces that do not tile their tensor in order, group ranges that are not the
+ * consecutive ranges of their tensors' pieces, an 8-byte misaligned or short `work`.  16-byte accesses are used where a tensor's four
+ * pointers are 16-byte (shadow 8-byte) aligned and the piece's offset is a multiple of 4, element accesses otherwise. */
+#define VK_LAMB_CLASSES 64
+#define VK_LAMB_PIECE 1024
+#define VK_LAMB_ADAM_W_MODE 1
+#define VK_LAMB_GRAD_AVERAGING 2
+#define VK_LAMB_GLOBAL_NORM 4
+typedef struct vk_lamb_tensor {
+    float* p;
+    const float* g;
+    float* m;
+    float* v;
+    void* shadow;               /* bf16 copy of p, refreshed by the pass that writes p, or NULL */
+    int64_t numel;
+    int32_t cls;                /* selects cls_lr / cls_wd / cls_bc1 / cls_bc2 */
+    int32_t group;              /* norm group */
+    int32_t piece0, npieces;    /* its pieces in the piece table */
+} vk_lamb_tensor;
+typedef struct vk_lamb_piece {
+    int64_t offset;             /* first element, within the tensor */
+    int32_t tensor;
+    int32_t count;              /* 1 .. VK_LAMB_PIECE */
+} vk_lamb_piece;
+typedef struct vk_lamb_group {
+    int32_t piece0, piece1;     /* [piece0, piece1): the pieces of the group's tensors */
+    float max_grad_norm;        /* <= 0: this group does not clip */
+    int32_t reserved_;
+} vk_lamb_group;
+typedef struct vk_lamb_args {
+    const vk_lamb_tensor* tensors;      /* HOST tables: checked before every launch */
+    const vk_lamb_piece* pieces;
+    const vk_lamb_group* groups;
+    const vk_lamb_tensor* d_tensors;    /* DEVICE copies of the same tables */
+    const vk_lamb_piece* d_pieces;
+    const vk_lamb_group* d_groups;
+    void* work;                 /* device scratch of vk_lamb_work_bytes(), 8-byte aligned */
+    int64_t work_bytes;
+    float* table;               /* device float[4 * ntensors], see above */
+    const float* clip;          /* device float[2] from the gradient-norm kernels or NULL */
+    int32_t ntensors, npieces, ngroups, flags;
+    float cls_lr[VK_LAMB_CLASSES];
+    float cls_wd[VK_LAMB_CLASSES];
+    float cls_bc1[VK_LAMB_CLASSES];
+    float cls_bc2[VK_LAMB_CLASSES];
+    float beta1, beta2, eps, grad_scale;
+} vk_lamb_args;
+/* Bytes of `work` for these host tables; <= 0 (and vk_last_error) for tables vk_lamb_step would refuse. */
+int64_t vk_lamb_work_bytes(const vk_lamb_tensor* tensors, int ntensors, const vk_lamb_piece* pieces, int npieces, const vk_lamb_group* groups, int ngroups);
+int vk_lamb_step(const vk_lamb_args* a, vk_stream_t s);
+/* The same step with hipEvents around its launches: ms[0 .. 5] = milliseconds of the gradient sums, the group sums, the clip divisors,
+ * stage 1, the per-tensor finish and stage 2 (0 for the three norm launches when no group clips).  Waits for the step; for
+ * tools/bench_lamb.py, not for training loops. */
+int vk_lamb_step_timed(const vk_lamb_args* a, vk_stream_t s, float* ms);
 /* y[i] += alpha * x[i], i < n (fp32).  n a multiple of 4; y and x 16-byte aligned (refused otherwise). */
 int vk_axpy_f32(float* y, const float* x, float alpha, int64_t n, vk_stream_t s);
 /* dst[i] = sum_{s < nslabs} src[s * slab_stride + i], i < n (fp32).  Combines the partial weight gradients of a

@@ -148,6 +148,34 @@ class RadamArgs(C.Structure):
                 ("one_minus_beta2", C.c_float), ("eps", C.c_float), ("grad_scale", C.c_float)]
 
 
+LAMB_CLASSES, LAMB_PIECE = 64, 1024      # VK_LAMB_CLASSES, VK_LAMB_PIECE
+LAMB_ADAM_W_MODE, LAMB_GRAD_AVERAGING, LAMB_GLOBAL_NORM = 1, 2, 4
+
+
+class LambTensor(C.Structure):
+    _fields_ = [("p", c_p), ("g", c_p), ("m", c_p), ("v", c_p), ("shadow", c_p), ("numel", C.c_int64), ("cls", i32), ("group", i32),
+                ("piece0", i32), ("npieces", i32)]
+
+
+class LambPiece(C.Structure):
+    _fields_ = [("offset", C.c_int64), ("tensor", i32), ("count", i32)]
+
+
+class LambGroup(C.Structure):
+    _fields_ = [("piece0", i32), ("piece1", i32), ("max_grad_norm", C.c_float), ("reserved_", i32)]
+
+
+class LambArgs(C.Structure):
+    _fields_ = [("tensors", c_p), ("pieces", c_p), ("groups", c_p), ("d_tensors", c_p), ("d_pieces", c_p), ("d_groups", c_p), ("work", c_p),
+                ("work_bytes", C.c_int64), ("table", c_p), ("clip", c_p), ("ntensors", i32), ("npieces", i32), ("ngroups", i32), ("flags", i32),
+                ("cls_lr", C.c_float * LAMB_CLASSES), ("cls_wd", C.c_float * LAMB_CLASSES), ("cls_bc1", C.c_float * LAMB_CLASSES),
+                ("cls_bc2", C.c_float * LAMB_CLASSES), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("grad_scale", C.c_float)]
+
+
+# ctypes mirrors by the header's struct names (the layout checks compile the header and compare sizeof)
+LAMB_STRUCTS = {"vk_lamb_tensor": LambTensor, "vk_lamb_piece": LambPiece, "vk_lamb_group": LambGroup, "vk_lamb_args": LambArgs}
+
+
 class GradSeedArgs(C.Structure):
     _fields_ = [("src", c_p), ("stride_b", C.c_int64), ("stride_l", C.c_int64), ("dst", c_p), ("y", c_p), ("B", i32), ("L", i32), ("H", i32),
                 ("row0", i32), ("ld", i32), ("ldy", i32), ("accumulate", i32), ("reserved_", i32)]
@@ -363,6 +391,9 @@ _sig("vk_knn_pool_work_bytes", C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int)
 _sig("vk_knn_pool", C.c_int, C.POINTER(KnnPoolArgs), c_p)
 _sig("vk_radam_step", C.c_int, C.POINTER(RadamArgs), c_p)
 _sig("vk_radam_step_list", C.c_int, C.POINTER(RadamArgs), c_p, C.c_int, C.c_int64, c_p)
+_sig("vk_lamb_work_bytes", C.c_int64, c_p, C.c_int, c_p, C.c_int, c_p, C.c_int)
+_sig("vk_lamb_step", C.c_int, C.POINTER(LambArgs), c_p)
+_sig("vk_lamb_step_timed", C.c_int, C.POINTER(LambArgs), c_p, C.POINTER(C.c_float))
 _sig("vk_grad_sqnorm_chunks", C.c_int, c_p, C.c_int64, C.c_int64, c_p, c_p, c_p)
 _sig("vk_grad_norm_from_chunks", C.c_int, c_p, C.c_int64, C.c_float, C.c_float, c_p, c_p)
 _sig("vk_axpy_f32", C.c_int, c_p, c_p, C.c_float, C.c_int64, c_p)
@@ -405,7 +436,7 @@ EXPORTS = ["vk_version", "vk_device_arch", "vk_last_error", "vk_set_seed", "vk_c
            "vk_relu_bwd_bf16", "vk_copy_async", "vk_select_rows", "vk_gather_rows", "vk_scatter_rows_add", "vk_xent_fwd",
            "vk_xent_bwd", "vk_kl_fwd", "vk_kl_bwd", "vk_loss_finalize", "vk_pool_mul_fwd", "vk_pool_mul_bwd",
            "vk_pool_fuse_fwd", "vk_pool_fuse_bwd", "vk_text_end_rows", "vk_vlbert_obj_ids", "vk_vlbert_positions", "vk_vis_loss_fwd", "vk_vis_loss_bwd", "vk_nce_negatives", "vk_task_loss_work_bytes", "vk_task_loss_fwd", "vk_task_loss_bwd",
-           "vk_mask_prep", "vk_mul_bf16", "vk_grad_norm_workspace_floats", "vk_grad_norm_clip", "vk_grad_norm_clip_masked", "vk_grad_sqnorm_chunks", "vk_grad_norm_from_chunks", "vk_adamw_step", "vk_adamw_step_on", "vk_adamw_step_list", "vk_grad_sqnorm_list", "vk_grad_sqnorm_list_work_floats", "vk_grad_seed", "vk_pair_gather", "vk_radam_step", "vk_radam_step_list",
+           "vk_mask_prep", "vk_mul_bf16", "vk_grad_norm_workspace_floats", "vk_grad_norm_clip", "vk_grad_norm_clip_masked", "vk_grad_sqnorm_chunks", "vk_grad_norm_from_chunks", "vk_adamw_step", "vk_adamw_step_on", "vk_adamw_step_list", "vk_grad_sqnorm_list", "vk_grad_sqnorm_list_work_floats", "vk_grad_seed", "vk_pair_gather", "vk_radam_step", "vk_radam_step_list", "vk_lamb_work_bytes", "vk_lamb_step", "vk_lamb_step_timed",
            "vk_axpy_f32", "vk_sum_slabs_f32", "vk_sum_slabs_bf16", "vk_memset_async", "vk_hold_cus", "vk_gate_wait", "vk_bump_u64", "vk_store_u64", "vk_gate_value", "vk_comm_standin", "vk_gemm_reserve_cus", "vk_side_tail", "vk_run_ops", "vk_run_ops_timed", "vk_side_join", "vk_side_join_from", "vk_side_stream", "vk_side_enable", "vk_concap_batch",
            "vk_lmdb_open", "vk_lmdb_close", "vk_lmdb_entries", "vk_lmdb_first", "vk_lmdb_next", "vk_lmdb_get", "vk_concap_record_decode", "vk_concap_records_decode", "vk_b64_decode",
            "vk_wordpiece_open", "vk_wordpiece_close", "vk_wordpiece_vocab_size", "vk_wordpiece_token_id", "vk_wordpiece_encode", "vk_wordpiece_encode_batch",

@@ -3,6 +3,7 @@
   AdamW                  pytorch_transformers.optimization.AdamW  (same constructor / param-group semantics)
   WarmupLinearSchedule   pytorch_transformers.optimization.WarmupLinearSchedule
   RAdam, PlainRAdam      volta.optimization.RAdam / PlainRAdam  (train_task.py:27,227-228; see RAdam)
+  LAMB                   apex.optimizers.FusedLAMB as the reference tree vendors it  (see LAMB)
   WarmupConstantSchedule pytorch_transformers.optimization.WarmupConstantSchedule  (train_task.py:24,233-234)
   clip_grad_norm_        torch.nn.utils.clip_grad_norm_
 
@@ -741,6 +742,335 @@ class PlainRAdam(RAdam):
     """volta.optimization.PlainRAdam (volta/optimization.py:96-169): RAdam with each parameter's step size from its own group's lr and
     step count, and no shared buffer.  Same kernels, same scope."""
     _plain = True
+
+
+# numpy mirrors of vk_lamb_tensor / vk_lamb_piece / vk_lamb_group (include/volta_hip.h): the tables are built as arrays, not row by row
+_LAMB_TENSOR = np.dtype([("p", "<u8"), ("g", "<u8"), ("m", "<u8"), ("v", "<u8"), ("shadow", "<u8"), ("numel", "<i8"), ("cls", "<i4"),
+                         ("group", "<i4"), ("piece0", "<i4"), ("npieces", "<i4")])
+_LAMB_PIECE = np.dtype([("offset", "<i8"), ("tensor", "<i4"), ("count", "<i4")])
+_LAMB_GROUP = np.dtype([("piece0", "<i4"), ("piece1", "<i4"), ("max_grad_norm", "<f4"), ("reserved_", "<i4")])
+assert (_LAMB_TENSOR.itemsize, _LAMB_PIECE.itemsize, _LAMB_GROUP.itemsize) == (C.sizeof(L.LambTensor), C.sizeof(L.LambPiece), C.sizeof(L.LambGroup))
+
+
+def lamb_tables(rows, max_norms, piece=L.LAMB_PIECE):
+    """The host tables of vk_lamb_step for `rows` = [(p, g, m, v, shadow or 0, numel, class, group)] (addresses as integers, groups
+    ascending) and the groups' max_grad_norm (<= 0 or None: no clipping): (tensors, pieces, groups) as numpy record arrays.  Every tensor
+    is tiled exactly once by consecutive pieces of at most `piece` elements, in offset order (64-bit offsets); a piece never crosses a
+    tensor, so tensors that share an arena chunk (the biases of a fused query / key / value slot) get pieces, and norms, of their own."""
+    T = np.zeros(len(rows), dtype=_LAMB_TENSOR)
+    for k, name in enumerate(("p", "g", "m", "v", "shadow", "numel", "cls", "group")):
+        T[name] = [r[k] for r in rows]
+    numel = T["numel"].astype(np.int64)
+    if len(rows) and (numel.min() < 0 or np.any(np.diff(T["group"]) < 0) or T["group"].min() < 0 or T["group"].max() >= len(max_norms)):
+        raise ValueError("lamb_tables: negative numel, or groups that do not ascend within 0 .. %d" % (len(max_norms) - 1))
+    npc = (numel + piece - 1) // piece
+    first = np.concatenate([np.zeros(1, dtype=np.int64), np.cumsum(npc)])
+    if first[-1] >= 2 ** 31:
+        raise ValueError("lamb_tables: %d pieces" % first[-1])
+    T["piece0"], T["npieces"] = first[:-1], npc
+    P = np.zeros(int(first[-1]), dtype=_LAMB_PIECE)
+    owner = np.repeat(np.arange(len(rows), dtype=np.int64), npc)
+    P["tensor"] = owner
+    P["offset"] = (np.arange(len(P), dtype=np.int64) - first[owner]) * piece
+    P["count"] = np.minimum(piece, numel[owner] - P["offset"])
+    G = np.zeros(len(max_norms), dtype=_LAMB_GROUP)
+    G["max_grad_norm"] = [float(x) if x is not None and x > 0 else 0.0 for x in max_norms]
+    ends = np.zeros(len(max_norms), dtype=np.int64)          # pieces of groups 0 .. n, cumulative
+    np.add.at(ends, T["group"], npc)
+    ends = np.cumsum(ends)
+    G["piece1"] = ends
+    G["piece0"][1:] = ends[:-1]
+    return T, P, G
+
+
+class LAMB(Optimizer):
+    """apex.optimizers.FusedLAMB as the reference tree vendors it (apex/apex/optimizers/fused_lamb.py over apex/csrc/multi_tensor_lamb.cu):
+    same constructor, param-group semantics (`group["step"]` counts per group, and advances every step) and state_dict layout; Adam
+    moments, then one trust ratio lr * |p| / |update| per parameter tensor -- query, key and value of a fused slot are three tensors with
+    three ratios.  One vk_lamb_step call per step (csrc/lamb.hip: six launches whatever the number of parameters) over the arena views and
+    the tensors outside the arena alike; lr, step, the clip divisor and a deferred clip_grad_norm_ coefficient reach the kernels without a
+    host read or a rebuilt table.  The semantics are spelled out at vk_lamb_step in include/volta_hip.h.
+
+    Differences from apex, on purpose:
+      * `.grad` keeps its bits across step() (apex overwrites it with the update): gradient accumulation and the data-parallel reducer
+        read that arena.  The second stage recomputes the update instead.
+      * max_grad_norm None or <= 0 disables this optimizer's own clipping (the vendored kernel would divide by it).
+      * global_grad_norm=True takes ONE gradient norm over all groups, as later apex versions do; the default, False, is the vendored
+        behaviour: one norm per param group, over the tensors of that group stepped this call.
+      * the norm is that of the gradient the step consumes: g * grad_scale * (deferred clip coefficient).
+    Accepts what RAdam accepts: one volta_amd model's parameters plus contiguous CUDA fp32 tensors.  lr, weight_decay and max_grad_norm
+    may differ per group (at most 64 distinct (lr, weight_decay, step) combinations in one step); betas, eps, bias_correction and
+    grad_averaging are common to all groups.  Out of scope (raise): amsgrad (RuntimeError, as apex), DistributedDataParallel(mode="zero1")
+    (NotImplementedError), and there is no overlap_with_forward form."""
+
+    def __init__(self, params, lr=1e-3, bias_correction=True, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.01, amsgrad=False,
+                 adam_w_mode=True, grad_averaging=True, set_grad_none=True, max_grad_norm=1.0, global_grad_norm=False):
+        if amsgrad:
+            raise RuntimeError("volta_amd.LAMB does not support the AMSGrad variant.")
+        if lr < 0.0:
+            raise ValueError("Invalid learning rate: {} - should be >= 0.0".format(lr))
+        if not 0.0 <= betas[0] < 1.0:
+            raise ValueError("Invalid beta parameter: {} - should be in [0.0, 1.0[".format(betas[0]))
+        if not 0.0 <= betas[1] < 1.0:
+            raise ValueError("Invalid beta parameter: {} - should be in [0.0, 1.0[".format(betas[1]))
+        if not 0.0 <= eps:
+            raise ValueError("Invalid epsilon value: {} - should be >= 0.0".format(eps))
+        super().__init__(params, dict(lr=lr, bias_correction=bias_correction, betas=betas, eps=eps, weight_decay=weight_decay,
+                                      grad_averaging=grad_averaging, max_grad_norm=max_grad_norm))
+        self.adam_w_mode = 1 if adam_w_mode else 0
+        self.set_grad_none = set_grad_none
+        self.global_grad_norm = bool(global_grad_norm)
+        self._hyper()
+        self._fused = None
+        self._pending = None        # a state loaded before the model was on the GPU: applied at the first setup (see RAdam)
+        try:                        # clip_grad_norm_ defers to this optimizer (see AdamW.__init__)
+            model, arena, _ = _split_params([p for g in self.param_groups for p in g["params"]])
+        except RuntimeError:
+            model = arena = None
+        if arena is not None:
+            self._refuse_zero1(model)
+            arena._vk_adamw = weakref.ref(self)
+
+    def _hyper(self):
+        """(beta1, beta2, eps, bias_correction, grad_averaging) common to all groups: one call steps all of them."""
+        hs = {(tuple(g["betas"]), g["eps"], bool(g["bias_correction"]), bool(g["grad_averaging"])) for g in self.param_groups}
+        if len(hs) != 1:
+            raise RuntimeError("volta_amd.LAMB: betas / eps / bias_correction / grad_averaging must be common to all groups (got %s)" % sorted(hs))
+        (b1, b2), eps, bc, ga = hs.pop()
+        return float(b1), float(b2), float(eps), bc, ga
+
+    @staticmethod
+    def _refuse_zero1(model):
+        red = getattr(getattr(model, "_ddp", None), "reducer", None)
+        if red is not None and red.mode == "zero1":
+            raise NotImplementedError("volta_amd.LAMB: data-parallel mode 'zero1' shards the optimizer state for AdamW only, and a trust ratio "
+                                      "needs whole tensors; use mode 'allreduce' or 'rs_ag'")
+
+    def _setup(self):
+        allp = [p for g in self.param_groups for p in g["params"]]
+        labels = ["param_groups[%d]['params'][%d]" % (gi, i) for gi, g in enumerate(self.param_groups) for i in range(len(g["params"]))]
+        model, arena, foreign = _split_params(allp, labels)
+        if arena is None and not foreign:
+            raise RuntimeError("volta_amd.LAMB: no parameters")
+        byptr = {p.data_ptr(): n for n, p in arena.params.items()} if arena is not None else {}
+        fids = {id(p) for p in foreign}
+        ents = []                   # per parameter in param_groups order: (group index, parameter, arena name or None, moments outside the arena)
+        for gi, g in enumerate(self.param_groups):
+            for p in g["params"]:
+                if id(p) in fids:
+                    ents.append((gi, p, None, dict(m=torch.zeros_like(p), v=torch.zeros_like(p))))
+                else:
+                    ents.append((gi, p, byptr[p.data_ptr()], None))
+        f = dict(model=model, arena=arena, ents=ents, stepped=[False] * len(ents), tables={}, last=None)
+        if arena is not None:
+            arena._vk_adamw = weakref.ref(self)
+            f.update(m=torch.zeros_like(arena.master), v=torch.zeros_like(arena.master))
+        self._fused = f
+        if self._pending is not None:
+            self._apply_state(self._pending)
+            self._pending = None
+
+    def _grad_names(self):
+        """Names of this optimizer's parameters that carry a gradient now (what a deferred clip coefficient must have been computed over)."""
+        return frozenset(n if n is not None else ("foreign", id(p)) for _, p, n, _ in self._fused["ents"] if p.grad is not None)
+
+    def _moments(self, i):
+        """(exp_avg, exp_avg_sq) of parameter i as flat views."""
+        f = self._fused
+        _, p, n, fr = f["ents"][i]
+        if fr is not None:
+            return fr["m"].view(-1), fr["v"].view(-1)
+        o, k = f["arena"].offset[n], p.numel()
+        return f["m"][o:o + k], f["v"][o:o + k]
+
+    def _tables(self, key, rows, labels, max_norms, device):
+        """Host and device tables, scratch and ratio table for this (liveness, pointer, class) pattern: built once, reused while it holds."""
+        f = self._fused
+        t = f["tables"].get(key)
+        if t is None:
+            T, P, G = lamb_tables(rows(), max_norms)
+            nbytes = L.lib.vk_lamb_work_bytes(T.ctypes.data, len(T), P.ctypes.data, len(P), G.ctypes.data, len(G))
+            if nbytes <= 0:
+                raise L.VoltaHipError(L.lib.vk_last_error().decode())
+            dev = [torch.from_numpy(x.view(np.uint8).reshape(-1).copy()).to(device) for x in (T, P, G)]
+            if len(f["tables"]) > 4:
+                f["tables"].clear()
+            t = f["tables"][key] = dict(host=(T, P, G), dev=dev, work=torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=device), nbytes=nbytes,
+                                        table=torch.zeros(len(T), 4, device=device), labels=labels())
+        return t
+
+    @torch.no_grad()
+    def step(self, closure=None, grad_scale=1.0):
+        loss = closure() if closure is not None else None
+        if self._fused is None:
+            self._setup()
+        f = self._fused
+        arena, ents = f["arena"], f["ents"]
+        self._refuse_zero1(f["model"])
+        b1, b2, eps, bias_correction, grad_averaging = self._hyper()
+        for g in self.param_groups:                    # apex: every group's counter advances, with or without gradients in it
+            g["step"] = g.get("step", 0) + 1
+        if arena is not None and f.get("fixed") is None:
+            # what does not change while the arena stands: per arena parameter (p, expected g, m, v, shadow, numel)
+            pb, gb, mb, vb, sb = (x.data_ptr() for x in (arena.master, arena.grad, f["m"], f["v"], arena.shadow))
+            f["fixed"] = [None if n is None else (pb + 4 * arena.offset[n], gb + 4 * arena.offset[n], mb + 4 * arena.offset[n], vb + 4 * arena.offset[n],
+                                                  sb + 2 * arena.offset[n], p.numel()) for _, p, n, _ in ents]
+        fixed = f.get("fixed")
+        live, fptr, groups_live = [], [], set()
+        for i, (gi, p, n, fr) in enumerate(ents):
+            g = p.grad
+            live.append(g is not None)
+            if g is None:
+                continue
+            groups_live.add(gi)
+            if n is not None:
+                if g.data_ptr() != fixed[i][1]:
+                    raise RuntimeError("volta_amd.LAMB: the gradient of %s is not the engine's arena view (a foreign tensor was assigned to "
+                                       ".grad); run backward through the model, or zero_grad(set_to_none=True)" % n)
+            elif g.dtype != torch.float32 or not g.is_contiguous() or g.shape != p.shape or g.device != p.device:
+                raise RuntimeError("volta_amd.LAMB: the gradient of a tensor outside the arena must be a contiguous float32 tensor of its shape")
+            else:
+                fptr.append((p.data_ptr(), g.data_ptr()))
+        if not groups_live:
+            f["last"] = None
+            return loss
+        # classes: what the kernels look up per tensor -- (lr, weight decay, step count) of its group; groups without a live tensor need none
+        classes, cls_of_group = {}, {}
+        for gi in sorted(groups_live):
+            g = self.param_groups[gi]
+            key = (float(g["lr"]), float(g["weight_decay"]), int(g["step"]) if bias_correction else 0)
+            if key not in classes:
+                if len(classes) == L.LAMB_CLASSES:
+                    raise RuntimeError("volta_amd.LAMB: more than %d distinct (lr, weight decay, step count) classes in one step" % L.LAMB_CLASSES)
+                classes[key] = len(classes)
+            cls_of_group[gi] = classes[key]
+        max_norms = tuple(g["max_grad_norm"] for g in self.param_groups)
+
+        def rows():
+            out, k = [], 0
+            for i, ((gi, p, n, fr), l) in enumerate(zip(ents, live)):
+                if not l:
+                    continue
+                if n is not None:
+                    out.append(fixed[i] + (cls_of_group[gi], gi))
+                else:
+                    out.append(fptr[k] + (fr["m"].data_ptr(), fr["v"].data_ptr(), 0, p.numel(), cls_of_group[gi], gi))
+                    k += 1
+            return out
+
+        def labels():
+            return [n if n is not None else i for i, ((_, _, n, _), l) in enumerate(zip(ents, live)) if l]
+
+        key = (tuple(live), tuple(fptr), tuple(sorted(cls_of_group.items())), max_norms)
+        t = self._tables(key, rows, labels, max_norms, ents[0][1].device)
+        a = L.LambArgs()
+        T, P, G = t["host"]
+        a.tensors, a.pieces, a.groups = T.ctypes.data, P.ctypes.data, G.ctypes.data
+        a.d_tensors, a.d_pieces, a.d_groups = (x.data_ptr() for x in t["dev"])
+        a.work, a.work_bytes, a.table = t["work"].data_ptr(), t["nbytes"], t["table"].data_ptr()
+        a.ntensors, a.npieces, a.ngroups = len(T), len(P), len(G)
+        a.flags = ((L.LAMB_ADAM_W_MODE if self.adam_w_mode else 0) | (L.LAMB_GRAD_AVERAGING if grad_averaging else 0)
+                   | (L.LAMB_GLOBAL_NORM if self.global_grad_norm else 0))
+        b1f, b2f = float(np.float32(b1)), float(np.float32(b2))      # the betas the kernels use: apex takes its powers of the fp32 values too
+        for (lr, wd, st), c in classes.items():
+            a.cls_lr[c], a.cls_wd[c] = lr, wd
+            a.cls_bc1[c], a.cls_bc2[c] = (1.0 - b1f ** st, 1.0 - b2f ** st) if bias_correction else (1.0, 1.0)
+        a.beta1, a.beta2, a.eps, a.grad_scale = b1, b2, eps, grad_scale
+        clip = None
+        if arena is not None:
+            pend = getattr(arena, "pending_clip", None)
+            if pend is not None:
+                if pend[1] == self._grad_names():
+                    clip = pend[0]             # computed over exactly the gradients this step consumes: folded into the pass
+                else:
+                    flush_clip(arena)
+            arena.pending_clip = None
+            arena.sync_optimizer()
+        a.clip = clip.data_ptr() if clip is not None else None
+        L.check(L.lib.vk_lamb_step(C.byref(a), L.stream_ptr()))
+        if arena is not None and any(l and e[2] is not None for l, e in zip(live, ents)):
+            arena.mark_shadow_fresh()          # stage 2 refreshed the bf16 copies of what it wrote
+        stepped = f["stepped"]
+        for i, l in enumerate(live):
+            if l:
+                stepped[i] = True
+        f["last"] = t
+        return loss
+
+    def trust_ratios(self):
+        """{arena name, or position in param_groups order for a tensor outside the arena: (ratio / lr, |p|, |update|)} of the last step --
+        |p| before the update; parameters skipped in that step are absent.  One device-to-host copy, made here and nowhere else."""
+        t = self._fused["last"] if self._fused is not None else None
+        if t is None:
+            return {}
+        rows = t["table"].cpu().tolist()
+        return {lab: (r[1], r[2], r[3]) for lab, r in zip(t["labels"], rows)}
+
+    def zero_grad(self, set_to_none=None):
+        if set_to_none is None:
+            set_to_none = self.set_grad_none
+        if self._fused is not None and self._fused["arena"] is not None:
+            self._fused["arena"].pending_clip = None
+        for g in self.param_groups:
+            for p in g["params"]:
+                if set_to_none:
+                    p.grad = None
+                elif p.grad is not None:
+                    p.grad.zero_()
+
+    def synchronize(self):
+        if self._fused is not None and self._fused["arena"] is not None:
+            self._fused["arena"].sync_optimizer()
+
+    # ---- checkpoints: apex's layout -- param_groups[i]["step"], and {"exp_avg", "exp_avg_sq"} per parameter that has stepped, indexed in
+    # param_groups order
+    def state_dict(self):
+        self.synchronize()
+        sd = super().state_dict()
+        f = self._fused
+        if f is None:
+            sd["state"] = {i: {k: v.clone() for k, v in st.items()} for i, st in (self._pending or {}).items()}
+            return sd
+        out = {}
+        for i, (_, p, _, _) in enumerate(f["ents"]):
+            if f["stepped"][i]:
+                m, v = self._moments(i)
+                out[i] = {"exp_avg": m.view(p.shape).clone(), "exp_avg_sq": v.view(p.shape).clone()}
+        sd["state"] = out
+        return sd
+
+    def load_state_dict(self, state_dict):
+        self.synchronize()
+        state = state_dict.get("state", {})
+        super().load_state_dict({"state": {}, "param_groups": state_dict["param_groups"]})
+        self._hyper()
+        allp = [p for g in self.param_groups for p in g["params"]]
+        st = {}
+        for k, s in state.items():
+            i = int(k)
+            if not 0 <= i < len(allp):
+                raise ValueError("volta_amd.LAMB.load_state_dict: state for parameter %d, the optimizer has %d" % (i, len(allp)))
+            if s["exp_avg"].numel() != allp[i].numel() or s["exp_avg_sq"].numel() != allp[i].numel():
+                raise ValueError("volta_amd.LAMB.load_state_dict: parameter %d's state does not fit it (%d / %d elements for %d)"
+                                 % (i, s["exp_avg"].numel(), s["exp_avg_sq"].numel(), allp[i].numel()))
+            st[i] = {"exp_avg": s["exp_avg"].detach().float().cpu().clone(), "exp_avg_sq": s["exp_avg_sq"].detach().float().cpu().clone()}
+        if self._fused is None and not all(p.device.type == "cuda" for p in allp):
+            self._pending = st          # the model is not on the GPU yet: applied at the first setup
+            return
+        if self._fused is None:
+            self._setup()
+        self._apply_state(st)
+
+    def _apply_state(self, st):
+        f = self._fused
+        for i in range(len(f["ents"])):
+            s = st.get(i)
+            dm, dv = self._moments(i)
+            if s is None:
+                dm.zero_(); dv.zero_()
+            else:
+                dm.copy_(s["exp_avg"].reshape(-1)); dv.copy_(s["exp_avg_sq"].reshape(-1))
+            f["stepped"][i] = s is not None
 
 
 class WarmupLinearSchedule(LambdaLR):
