@@ -1011,6 +1011,69 @@ typedef struct vk_task_batch_args {
 } vk_task_batch_args;
 int vk_task_batch(const vk_task_batch_args* a, vk_stream_t s);
 
+/* The same assembler over a device-resident image store (TaskLoader(resident_bytes > 0)): outputs and every arithmetic rule are those of
+ * vk_task_batch; the only difference is where image slot s comes from.  It is read from one of two byte regions -- base[0] = the loader's
+ * resident pool, base[1] = this batch's scratch -- through per-slot byte offsets: features [n[s], F] fp32 packed at feat_off[s], pixel boxes
+ * [n[s], 4] fp32 packed at box_off[s] and the image's global row [F] fp32 at mean_off[s] of region where[s].  There is no Rcap: n is bounded
+ * by the region.  mean_off is read only when add_global != 0.
+ *   vk_task_pool_means  computes the global row of the `nslots` slots a device list names (the newly filled images) and stores it at their
+ *                       mean_off: rows added in order in fp32, then one correctly rounded division by n, as vk_task_batch's mean launch does.
+ *                       A list entry outside [0, S) is skipped.  It is the only call that writes into the regions.
+ *   vk_task_batch_pool  one launch; reads the stored global rows and launches no mean kernel, so a resident image's mean is never recomputed.
+ * The slot tables live in device memory and are not trusted: a slot whose `where` is not 0 or 1, whose n is negative, whose feat_off, box_off
+ * or (add_global != 0, and always in vk_task_pool_means) mean_off is not 16-byte aligned, or whose range off + n * F * 4 (features),
+ * off + n * 16 (boxes) or off + F * 4 (mean) leaves bytes[where] is treated as absent: no segment takes rows from it (they come out zero,
+ * or from an earlier overlapping segment), vk_task_pool_means writes nothing for it, and nothing of it is read. */
+typedef struct vk_task_pool_args {
+    const uint8_t* base[2];          /* 0 = the resident pool, 1 = this batch's scratch; 16-byte aligned */
+    uint64_t bytes[2];
+    const int32_t* where;            /* [S] 0 | 1 */
+    const uint64_t* feat_off;        /* [S] */
+    const uint64_t* box_off;         /* [S] */
+    const uint64_t* mean_off;        /* [S] */
+    const int32_t* n;                /* [S] */
+    const int32_t* wh;               /* [S, 2] */
+    const int32_t* segs;             /* [N, VK_TASK_MAX_SEGS, 4] */
+    const int32_t* mask_count;       /* [N] */
+    float* features;
+    float* spatials;
+    int64_t* image_mask;
+    float* target;
+    const int32_t* csr;              /* [B + 1] */
+    const int32_t* labels;
+    const float* scores;
+    const float* ref_box;            /* [N, 4] pixels */
+    int32_t S, F, N, R, B, num_locs, add_global, target_kind, num_labels;
+} vk_task_pool_args;
+int vk_task_batch_pool(const vk_task_pool_args* a, vk_stream_t s);
+int vk_task_pool_means(const vk_task_pool_args* a, const int32_t* slots /* device */, int nslots, vk_stream_t s);
+
+/* Base64 on the device (csrc/b64.hip): every text field of a batch, ragged lengths included, from a device copy of the text (`text`,
+ * text_bytes) to its place in `dst` (dst_bytes), one decoding launch for all `njobs` jobs.  Job j decodes the nsig characters at text_off
+ * into want_bytes bytes at dst_off.
+ *   grammar     the canonical subset of what vk_b64_decode accepts: the standard and the url-safe alphabet, NO whitespace.  nsig counts the
+ *               significant characters: the caller strips up to two trailing '=' by looking at the last two bytes only.  Any other byte in
+ *               [0, nsig) -- an interior '=', a line break -- is an error.  The unused low bits of the last character are ignored, as on
+ *               the host.
+ *   want_bytes  a multiple of 4 (the payloads are fp32) and equal to nsig * 3 / 4 rounded down.
+ *   alignment   text, dst, text_off and dst_off are 16-byte aligned.
+ *   job table   device memory, not trusted: a job whose text range leaves [0, text_bytes), whose destination range leaves [0, dst_bytes),
+ *               whose lengths disagree (want_bytes not as above, nsig > max_nsig, nsig > 2^31 - 1) or whose offsets are misaligned writes
+ *               nothing and gets status 0xFFFFFFFE.  No table content makes the kernels read or write out of bounds.
+ *   max_nsig    the largest nsig of the table (sizes the grid); at most 2^31 - 1.
+ *   status[j]   fully written by the call (the caller passes uninitialised memory): 0 = decoded, otherwise 1 + the offset of the first
+ *               (smallest-offset) offending byte, or 0xFFFFFFFE as above.  The destination bytes of a flagged job are unspecified; bytes
+ *               outside every job's destination range are never touched.
+ * njobs == 0 returns 0 without a launch; at most 65535 jobs per call. */
+typedef struct vk_b64_job {
+    uint64_t text_off;
+    uint64_t dst_off;
+    uint32_t nsig;
+    uint32_t want_bytes;
+} vk_b64_job;
+int vk_b64_decode_device(const uint8_t* text, uint64_t text_bytes, uint8_t* dst, uint64_t dst_bytes, const vk_b64_job* jobs /* device */, int njobs,
+                         uint32_t max_nsig, uint32_t* status /* device [njobs] */, vk_stream_t s);
+
 /* Retrieval ranks (eval_retrieval.py:200-263 without a sort).  One total order defines every output: the key of (score s, index j) is
  * sortable(s) << 32 | (0xFFFFFFFF - j), sortable: fp32 -> uint32 monotone, -0.0 == +0.0, every NaN lowest; a larger key ranks earlier, which
  * is the position in np.argsort(-s, kind="stable").
@@ -1178,6 +1241,17 @@ typedef struct vk_task_image {
     int32_t rows, F;
 } vk_task_image;
 int vk_task_images_stage(const vk_task_image* jobs, int n, int threads, int* failed);
+
+/* The text fields themselves, for the device decoder (vk_b64_decode_device): field j's first nsig bytes are copied to arena + dst_off, on
+ * `threads` host threads (at most 16) in ONE call.  The caller has stripped trailing '=' by length (nsig) and laid the fields out at 16-byte
+ * aligned offsets; a misaligned offset or a range that leaves [0, arena_bytes) is an error and nothing is copied.  The text is not looked
+ * at: validation is the device decoder's status word. */
+typedef struct vk_task_text {
+    const char* src;
+    uint64_t nsig;
+    uint64_t dst_off;
+} vk_task_text;
+int vk_task_texts_pack(const vk_task_text* jobs, int n, uint8_t* arena, uint64_t arena_bytes, int threads);
 
 #ifdef __cplusplus
 }

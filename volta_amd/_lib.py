@@ -205,6 +205,24 @@ class TaskImage(C.Structure):
                 ("rows", i32), ("F", i32)]
 
 
+class TaskPoolArgs(C.Structure):
+    _fields_ = [("base", c_p * 2), ("bytes", C.c_uint64 * 2)] + \
+               [(n, c_p) for n in ("where", "feat_off", "box_off", "mean_off", "n", "wh", "segs", "mask_count", "features", "spatials", "image_mask",
+                                   "target", "csr", "labels", "scores", "ref_box")] + \
+               [(n, i32) for n in ("S", "F", "N", "R", "B", "num_locs", "add_global", "target_kind", "num_labels")]
+
+
+class B64Job(C.Structure):
+    _fields_ = [("text_off", C.c_uint64), ("dst_off", C.c_uint64), ("nsig", C.c_uint32), ("want_bytes", C.c_uint32)]
+
+
+B64_REFUSED = 0xFFFFFFFE   # status of a job the device decoder's table check refuses
+
+
+class TaskText(C.Structure):
+    _fields_ = [("src", c_p), ("nsig", C.c_uint64), ("dst_off", C.c_uint64)]
+
+
 RANKS_MAX_TOPK = 64       # VK_RANKS_MAX_TOPK
 
 
@@ -362,6 +380,10 @@ _sig("vk_wordpiece_encode_batch", C.c_int, c_p, C.POINTER(C.c_char_p), C.POINTER
 _sig("vk_b64_decode", C.c_int, C.c_char_p, C.c_size_t, c_p, C.c_size_t, C.POINTER(C.c_size_t))
 _sig("vk_task_batch", C.c_int, C.POINTER(TaskBatchArgs), c_p)
 _sig("vk_task_images_stage", C.c_int, C.POINTER(TaskImage), C.c_int, C.c_int, C.POINTER(C.c_int))
+_sig("vk_task_batch_pool", C.c_int, C.POINTER(TaskPoolArgs), c_p)
+_sig("vk_task_pool_means", C.c_int, C.POINTER(TaskPoolArgs), c_p, C.c_int, c_p)
+_sig("vk_b64_decode_device", C.c_int, c_p, C.c_uint64, c_p, C.c_uint64, c_p, C.c_int, C.c_uint32, c_p, c_p)
+_sig("vk_task_texts_pack", C.c_int, C.POINTER(TaskText), C.c_int, c_p, C.c_uint64, C.c_int)
 _sig("vk_vlbert_positions", C.c_int, c_p, C.c_int, C.c_int, C.c_int, c_p, c_p, c_p)
 _sig("vk_vis_loss_fwd", C.c_int, C.POINTER(VisLossArgs), c_p)
 _sig("vk_vis_loss_bwd", C.c_int, C.POINTER(VisLossArgs), c_p, C.c_int, c_p, c_p)
@@ -442,7 +464,7 @@ EXPORTS = ["vk_version", "vk_device_arch", "vk_last_error", "vk_set_seed", "vk_c
            "vk_wordpiece_open", "vk_wordpiece_close", "vk_wordpiece_vocab_size", "vk_wordpiece_token_id", "vk_wordpiece_encode", "vk_wordpiece_encode_batch",
            "vk_lora_fwd", "vk_lora_bwd", "vk_lora_bwd_work_bytes", "vk_lora_proj_fwd", "vk_lora_proj_bwd", "vk_lora_proj_bwd_work_bytes",
            "vk_lora_fwd_drop", "vk_lora_bwd_drop", "vk_lora_proj_fwd_drop", "vk_lora_proj_bwd_drop",
-           "vk_task_batch", "vk_task_images_stage", "vk_retrieval_ranks", "vk_retrieval_ranks_shard_rows", "vk_retrieval_ranks_shard_cols", "vk_retrieval_ranks_finish", "vk_image_means", "vk_knn_pool_work_bytes", "vk_knn_pool"]
+           "vk_task_batch", "vk_task_images_stage", "vk_task_batch_pool", "vk_task_pool_means", "vk_b64_decode_device", "vk_task_texts_pack", "vk_retrieval_ranks", "vk_retrieval_ranks_shard_rows", "vk_retrieval_ranks_shard_cols", "vk_retrieval_ranks_finish", "vk_image_means", "vk_knn_pool_work_bytes", "vk_knn_pool"]
 
 
 def check(rc):

@@ -637,3 +637,29 @@ extern "C" int vk_task_images_stage(const vk_task_image* jobs, int n, int thread
     // re-run the failing image on this thread: deterministic, and leaves its message in this thread's vk_last_error()
     return task_image_stage(&jobs[bad.load()]) ? -1 : set_error("vk_task_images_stage: image %d failed", bad.load());
 }
+
+// The text fields of a batch into the pinned arena that the device decoder's one H2D copy takes (TaskLoader with resident_bytes > 0): plain
+// copies, the padding already stripped by length.  Nothing looks at the text here: that would cost what the host decode costs.
+extern "C" int vk_task_texts_pack(const vk_task_text* jobs, int n, uint8_t* arena, uint64_t arena_bytes, int threads) {
+    if (n <= 0) return 0;
+    if (!jobs || !arena) return set_error("vk_task_texts_pack: null argument");
+    for (int i = 0; i < n; ++i) {
+        if (!jobs[i].src && jobs[i].nsig) return set_error("vk_task_texts_pack: field %d has no text", i);
+        if ((jobs[i].dst_off & 15) || jobs[i].dst_off > arena_bytes || jobs[i].nsig > arena_bytes - jobs[i].dst_off)
+            return set_error("vk_task_texts_pack: field %d (%llu bytes at offset %llu) is misaligned or leaves the arena of %llu bytes", i,
+                             (unsigned long long)jobs[i].nsig, (unsigned long long)jobs[i].dst_off, (unsigned long long)arena_bytes);
+    }
+    if (threads < 1) threads = 1;
+    if (threads > 16) threads = 16;
+    if (threads > n) threads = n;
+    std::atomic<int> next{0};
+    auto work = [&]() {
+        for (int i = next.fetch_add(1); i < n; i = next.fetch_add(1))
+            if (jobs[i].nsig) memcpy(arena + jobs[i].dst_off, jobs[i].src, (size_t)jobs[i].nsig);
+    };
+    std::vector<std::thread> pool;
+    for (int t = 1; t < threads; ++t) pool.emplace_back(work);
+    work();
+    for (auto& th : pool) th.join();
+    return 0;
+}

@@ -15,7 +15,9 @@ Same constructor signature, `len`, `num_labels`, `label2ans` / `ans2label` and a
 the reference's tuple with its dtypes and shapes, computed on the host with numpy: that is the compatibility surface (a torch DataLoader over
 it works) and what the CPU tests pin against recorded reference outputs.  `TaskLoader` yields the collated batch on the GPU without building
 samples in Python: image records are base64-decoded by one native call per batch into pinned staging (`vk_task_images_stage`), copied once,
-and padded / normalised / masked / targeted by `vk_task_batch` (csrc/taskbatch.hip).
+and padded / normalised / masked / targeted by `vk_task_batch` (csrc/taskbatch.hip).  `TaskLoader(resident_bytes=N)` keeps the images in a
+device-resident pool instead: the text fields are decoded on the device (`vk_b64_decode_device`, csrc/b64.hip) during the first epoch and
+`vk_task_batch_pool` reads the pool, so later epochs send only the small integer tables.
 
 Tokenisation happens once in the constructor (one native call with a `WordPieceTokenizer`).  The reference's `cache/*.pkl` of tokenised
 entries is neither read nor written: it holds pickled torch tensors tied to another tokenizer object, and tokenising a whole split takes well
@@ -758,6 +760,87 @@ class _PinnedPool:
         return out
 
 
+def _b64_nsig(text):
+    """significant characters of a base64 text: its length without up to two trailing '=' (only the last two characters are looked at)"""
+    return len(text) - (2 if text[-2:] in ("==", b"==") else 1 if text[-1:] in ("=", b"=") else 0)
+
+
+def _text_layout(texts):
+    """texts: one base64 field after the other -> ([(field, nsig, arena offset)], arena bytes): the fields packed without their padding at
+    16-byte aligned offsets, as `vk_task_texts_pack` copies them and `vk_b64_decode_device` reads them"""
+    fields, at = [], 0
+    for t in texts:
+        nsig = _b64_nsig(t)
+        fields.append((t, nsig, at))
+        at += -(-nsig // 16) * 16
+    return fields, at
+
+
+_as_utf8 = C.pythonapi.PyUnicode_AsUTF8AndSize          # the str's own buffer for an ASCII str (CPython keeps UTF-8 == the compact ASCII data)
+_as_utf8.argtypes, _as_utf8.restype = [C.py_object, C.POINTER(C.c_ssize_t)], C.c_void_p
+
+
+def _text_address(text):
+    """(address of the field's bytes, the object that keeps them alive).  A `str` is read in place -- no `encode` copy -- when it is ASCII;
+    anything else takes the `encode("ascii")` of the host path, with its exception."""
+    if isinstance(text, str):
+        size = C.c_ssize_t()
+        p = _as_utf8(text, C.byref(size))
+        if p and size.value == len(text):
+            return p, text
+        text = text.encode("ascii")
+    else:
+        text = bytes(text)
+    return C.cast(C.c_char_p(text), C.c_void_p).value, text
+
+
+class _ResidentPool:
+    """Bookkeeping of the device-resident image store of `TaskLoader(resident_bytes > 0)`: a bump allocator over `capacity` bytes of ONE device
+    tensor (16-byte aligned offsets, no eviction, no free) and the dictionary image id -> (feat_off, box_off, mean_off, n, w, h).  An image
+    occupies one stretch: features [n, F] | global row [F] | boxes [n, 4], fp32.  Offsets are reserved while a batch is put together and
+    committed to the dictionary only after its decode came back clean; `rollback(mark)` gives the stretches of a failed batch back.  All
+    reservations, commits and rollbacks come from the consumer's thread, one batch after the other; the prefetch thread only reads the
+    dictionary, under the lock."""
+
+    ALIGN = 16
+
+    def __init__(self, capacity):
+        self.capacity, self.used, self.items, self.lock = int(capacity), 0, {}, threading.Lock()
+
+    @staticmethod
+    def layout(at, n, F):
+        """(feat_off, box_off, mean_off, bytes) of an image of n regions placed at byte `at`"""
+        feat, mean = n * F * 4, F * 4
+        return at, at + feat + mean, at + feat, feat + mean + n * 16
+
+    def reserve(self, nbytes):
+        """offset of `nbytes` fresh bytes, or None when the pool cannot hold them"""
+        at = -(-self.used // self.ALIGN) * self.ALIGN
+        if at + nbytes > self.capacity:
+            return None
+        self.used = at + nbytes
+        return at
+
+    def mark(self):
+        return self.used
+
+    def rollback(self, mark):
+        assert 0 <= mark <= self.used
+        self.used = mark
+
+    def get(self, image_id):
+        with self.lock:
+            return self.items.get(image_id)
+
+    def commit(self, entries):
+        with self.lock:
+            self.items.update(entries)
+
+    def __len__(self):
+        with self.lock:
+            return len(self.items)
+
+
 class ImageStager:
     """The batch form of `ImageFeaturesH5Reader.__getitem__`: for a list of distinct image ids, the records are looked up in the LMDB mapping
     and unpickled in Python, then ONE native call (`vk_task_images_stage`, GIL released, up to `threads` host threads, never more than 16)
@@ -854,11 +937,26 @@ class TaskLoader:
     out are recorded on the consumer's stream.  `in_memory=True` decodes into a pinned pool keyed by image id instead (at most `pool_bytes`,
     `pool_bytes_used` reports it), so later epochs neither look up nor decode.
 
+    `resident_bytes > 0` keeps the images on the device instead: ONE device tensor of that many bytes is the resident pool.  The prefetch
+    thread looks up and unpickles only the images that are not resident yet and copies their two base64 text fields into a pinned text arena
+    (`vk_task_texts_pack`, no decode on the host); on the loader's stream one H2D copy of that arena, `vk_b64_decode_device` (straight into
+    the pool while the image fits, else into a scratch tensor of the staging set), `vk_task_pool_means` for the new images and
+    `vk_task_batch_pool` follow.  An image enters the pool's dictionary only after its decode's status words came back clean; a flagged job
+    (whitespace in the text, a corrupt record) sends the whole batch through the host path above, with nothing of it kept.  From the second
+    epoch on the host contributes the small integer tables and nothing else.  There is no eviction; `resident_bytes_used`,
+    `resident_images` and `stats` (decoded_images, resident_hits, scratch_images, host_fallback_batches) report what happened.  Outputs are
+    bit for bit those of the default path.  Not combinable with `in_memory`.
+
     `sampler`: anything iterable over indices with `len` (SequentialSampler / RandomSampler / DistributedSampler above; torch's work too);
     None = sequential."""
 
     def __init__(self, dataset, batch_size, sampler=None, drop_last=False, device="cuda", prefetch=2, threads=None, in_memory=False,
-                 pool_bytes=8 << 30):
+                 pool_bytes=8 << 30, resident_bytes=0):
+        resident_bytes = int(resident_bytes)
+        if resident_bytes < 0:
+            raise ValueError("resident_bytes = %d: the size of the device-resident image pool in bytes, 0 = none" % resident_bytes)
+        if resident_bytes and in_memory:
+            raise ValueError("resident_bytes > 0 keeps the images on the device; in_memory=True keeps them in pinned host memory: choose one")
         self.dataset, self.batch_size, self.drop_last, self.device = dataset, int(batch_size), bool(drop_last), device
         self.sampler = sampler if sampler is not None else SequentialSampler(len(dataset))
         self.prefetch = max(0, int(prefetch))
@@ -866,6 +964,12 @@ class TaskLoader:
         self.threads = self.stager.threads
         self._stream = None
         self._text_dev = None
+        self.resident_bytes = resident_bytes
+        self._resident = _ResidentPool(resident_bytes) if resident_bytes else None
+        self._pool_dev = None                # the resident pool: one uint8 device tensor, allocated at first use
+        self._arenas = [None] * (self.prefetch + 2)     # pinned text arenas, one per staging set
+        self._scratch = [None] * (self.prefetch + 2)    # device scratch for images the pool cannot hold, one per staging set
+        self.stats = dict(decoded_images=0, resident_hits=0, scratch_images=0, host_fallback_batches=0)
 
     def __len__(self):
         n = len(self.sampler)
@@ -875,9 +979,17 @@ class TaskLoader:
     def pool_bytes_used(self):
         return self.stager.pool_bytes_used
 
+    @property
+    def resident_bytes_used(self):
+        return self._resident.used if self._resident is not None else 0
+
+    @property
+    def resident_images(self):
+        return len(self._resident) if self._resident is not None else 0
+
     # ---- host side (prefetch thread)
-    def _stage(self, indices, which):
-        """Everything of one batch that the host contributes: decoded images (staging set `which` or the pool) and the small integer tables."""
+    def _batch_images(self, indices):
+        """per sample its image ids, the text rows of the batch, and the slot of every distinct image id"""
         ds = self.dataset
         per_sample, text_rows = [], []
         for i in indices:                    # a dataset with random negatives draws them in images(); text_rows() refers to that draw
@@ -887,7 +999,52 @@ class TaskLoader:
         for ids in per_sample:
             for iid in ids:
                 slot_of.setdefault(iid, len(slot_of))
+        return per_sample, text_rows, slot_of
+
+    def _stage(self, indices, which):
+        """Everything of one batch that the host contributes: decoded images (staging set `which` or the pool) and the small integer tables."""
+        per_sample, text_rows, slot_of = self._batch_images(indices)
         h = self.stager.stage(list(slot_of), which)
+        return self._tables(h, indices, per_sample, text_rows, slot_of)
+
+    def _stage_resident(self, indices, which):
+        """`_stage` of the device-resident path: nothing for an image the pool holds; for the others the record lookup and, in one native call,
+        their text fields packed into the pinned text arena of staging set `which`.  Where the images go is decided in `_produce`."""
+        per_sample, text_rows, slot_of = self._batch_images(indices)
+        order, F = list(slot_of), self.stager.F
+        S = len(order)
+        n, wh = np.zeros(S, np.int32), np.zeros((S, 2), np.int32)
+        known, fresh, texts = {}, [], []
+        for s, iid in enumerate(order):
+            e = self._resident.get(iid)
+            if e is not None:
+                n[s], wh[s], known[s] = e[3], (e[4], e[5]), e
+                continue
+            ft, bt, h, w = self.stager._record(iid)
+            rows = _b64_rows(bt, 16)
+            if _b64_rows(ft, 4 * F) != rows:
+                raise ValueError("image %r: %d feature rows, %d boxes" % (iid, _b64_rows(ft, 4 * F), rows))
+            n[s], wh[s] = rows, (w, h)
+            fresh.append(s)
+            texts += [ft, bt]
+        fields, arena_bytes = _text_layout(texts)
+        arena = self._arenas[which]
+        if arena is None or arena.numel() < arena_bytes:
+            arena = self._arenas[which] = torch.empty(max(arena_bytes, 16), dtype=torch.uint8, pin_memory=self.stager._pin)
+        jobs, alive = (L.TaskText * max(len(fields), 1))(), []
+        for j, (t, nsig, at) in enumerate(fields):
+            p, keep = _text_address(t)
+            alive.append(keep)
+            jobs[j] = L.TaskText(p, nsig, at)
+        if fields:
+            L.check(L.lib.vk_task_texts_pack(jobs, len(fields), C.c_void_p(arena.data_ptr()), arena.numel(), self.threads))
+        h = dict(S=S, n=n, wh=wh, order=order, known=known, fresh=fresh, fields=[(nsig, at) for _, nsig, at in fields], arena=arena,
+                 arena_bytes=arena_bytes, which=which, resident=True)
+        return self._tables(h, indices, per_sample, text_rows, slot_of)
+
+    def _tables(self, h, indices, per_sample, text_rows, slot_of):
+        """the small integer tables of a batch, added to `h` (which holds n and wh of the staged images) and packed into one pinned buffer"""
+        ds = self.dataset
         nl = h["n"] + (1 if ds._add_global_imgfeat is not None else 0)
         segs, counts = [], []
         for i, ids in zip(indices, per_sample):
@@ -921,15 +1078,86 @@ class TaskLoader:
     _TABLES = ("text_rows", "ids", "n", "wh", "segs", "counts", "csr", "labels", "scores", "ref_box")
     _TORCH = {np.dtype(np.int64): torch.int64, np.dtype(np.int32): torch.int32, np.dtype(np.float32): torch.float32}
 
-    def _assemble(self, h):
-        from . import ops
-        ds, dev = self.dataset, self.device
-        packed = h["packed"].to(dev, non_blocking=True)
+    def _device_tables(self, h):
+        packed = h["packed"].to(self.device, non_blocking=True)
 
         def table(k):
             at, size, dt, shape = h["layout"][k]
             return packed[at:at + size].view(self._TORCH[np.dtype(dt)]).view(shape)
 
+        return table
+
+    def _target_args(self, table):
+        ds = self.dataset
+        if ds.target_kind == "scatter":
+            return dict(scatter=(table("csr"), table("labels"), table("scores"), ds.num_labels))
+        if ds.target_kind == "iou":
+            return dict(ref_box=table("ref_box"))
+        return {}
+
+    def _assemble_resident(self, h):
+        """The device half of the resident path, on the loader's stream: where every image of the batch lives (pool, or this staging set's
+        scratch), one H2D copy of the text arena, the decode, the global rows of the new images, the batch.  Leaves in `h` what `_produce`
+        needs once the stream has been synchronised: the status words (pinned), the pool mark, the entries to commit."""
+        from . import ops
+        ds, dev, pool, F = self.dataset, self.device, self._resident, self.stager.F
+        S, n, order = h["S"], h["n"], h["order"]
+        if self._pool_dev is None:
+            self._pool_dev = torch.empty(self.resident_bytes, dtype=torch.uint8, device=dev)
+        h["mark"] = pool.mark()
+        where, offs = np.zeros(max(S, 1), np.int32), np.zeros((3, max(S, 1)), np.int64)     # offs: feat_off, box_off, mean_off
+        for s, e in h["known"].items():
+            offs[:, s] = e[:3]
+        jobs, entries, scratch_at = ([], []), {}, 0
+        for k, s in enumerate(h["fresh"]):
+            rows = int(n[s])
+            size = _ResidentPool.layout(0, rows, F)[3]
+            at = pool.reserve(size) if pool.get(order[s]) is None else None      # staged a second time by an earlier batch: decode into scratch
+            w = 0 if at is not None else 1
+            if at is None:
+                at, scratch_at = scratch_at, scratch_at + size
+            fo, bo, mo, _ = _ResidentPool.layout(at, rows, F)
+            if w == 0:
+                entries[order[s]] = (fo, bo, mo, rows, int(h["wh"][s, 0]), int(h["wh"][s, 1]))
+            where[s], offs[:, s] = w, (fo, bo, mo)
+            (nsig_f, at_f), (nsig_b, at_b) = h["fields"][2 * k], h["fields"][2 * k + 1]
+            jobs[w].extend([(at_f, fo, nsig_f, rows * F * 4), (at_b, bo, nsig_b, rows * 16)])
+        h["entries"], h["scratch_images"] = entries, len(jobs[1]) // 2
+        scratch = self._scratch[h["which"]]
+        if scratch_at and (scratch is None or scratch.numel() < scratch_at):
+            scratch = self._scratch[h["which"]] = torch.empty(scratch_at, dtype=torch.uint8, device=dev)
+        regions = (self._pool_dev, scratch)
+        # the tables of this half travel as one buffer as well: int64 offsets first, then the 24-byte job records, then the int32 lists
+        tabs = [ops.b64_jobs(j) for j in jobs]
+        parts = [offs.view(np.int32).reshape(-1)] + [t.numpy().reshape(-1) for t, _ in tabs] + [where, np.asarray(h["fresh"], np.int32)]
+        small = torch.from_numpy(np.concatenate(parts)).to(dev)
+        cuts = np.cumsum([0] + [p.size for p in parts])
+        part = lambda i: small[cuts[i]:cuts[i + 1]]
+        offs_d = part(0).view(torch.int64).view(3, -1)
+        where_d, fresh_d = part(3), part(4)
+        statuses = []
+        if h["fresh"]:
+            text = h["arena"][:max(h["arena_bytes"], 1)].to(dev, non_blocking=True)
+            for w in (0, 1):
+                if jobs[w]:
+                    statuses.append(ops.b64_decode_device(text, regions[w], part(1 + w).view(-1, 6), tabs[w][1]))
+        status = torch.cat(statuses) if statuses else torch.zeros(0, dtype=torch.int32, device=dev)
+        h["status"] = torch.empty(status.numel(), dtype=torch.int32, pin_memory=self.stager._pin)
+        h["status"].copy_(status, non_blocking=True)
+        table = self._device_tables(h)
+        n_d, wh_d = table("n"), table("wh")
+        if S == 0:
+            n_d, wh_d = torch.zeros(1, dtype=torch.int32, device=dev), torch.ones(1, 2, dtype=torch.int32, device=dev)
+        slots = (regions, where_d, offs_d[0], offs_d[1], offs_d[2], n_d, wh_d, F)
+        if ds._add_global_imgfeat is not None and h["fresh"]:
+            ops.task_pool_means(*slots, fresh_d)
+        out = ops.task_batch_pool(*slots, table("segs"), table("counts"), ds.block_rows, ds._num_locs, ds._add_global_imgfeat, **self._target_args(table))
+        return self._finish(h, table, out)
+
+    def _assemble(self, h):
+        from . import ops
+        ds, dev = self.dataset, self.device
+        table = self._device_tables(h)
         S = h["S"]
         if h["staged_all"]:                  # one copy per array, at the staging set's own width (rows >= n are never read)
             feat, boxes = (h["stage"][k][:max(S, 1)].to(dev, non_blocking=True) for k in ("feat", "boxes"))
@@ -943,12 +1171,13 @@ class TaskLoader:
         n, wh = table("n"), table("wh")
         if S == 0:
             n, wh = torch.zeros(1, dtype=torch.int32, device=dev), torch.ones(1, 2, dtype=torch.int32, device=dev)
-        kw = {}
-        if ds.target_kind == "scatter":
-            kw["scatter"] = (table("csr"), table("labels"), table("scores"), ds.num_labels)
-        elif ds.target_kind == "iou":
-            kw["ref_box"] = table("ref_box")
-        out = ops.task_batch(feat, boxes, n, wh, table("segs"), table("counts"), ds.block_rows, ds._num_locs, ds._add_global_imgfeat, **kw)
+        out = ops.task_batch(feat, boxes, n, wh, table("segs"), table("counts"), ds.block_rows, ds._num_locs, ds._add_global_imgfeat,
+                             **self._target_args(table))
+        return self._finish(h, table, out)
+
+    def _finish(self, h, table, out):
+        """the assembled image tensors joined with the text rows, the target and the ids: the batch tuple"""
+        ds, dev = self.dataset, self.device
         if self._text_dev is None:
             self._text_dev = tuple(torch.from_numpy(t).to(dev) for t in ds._text)
         tok, im, seg = (t.index_select(0, table("text_rows")) for t in self._text_dev)
@@ -968,11 +1197,32 @@ class TaskLoader:
         if self._stream is None:
             self._stream = torch.cuda.Stream()
         with torch.cuda.stream(self._stream):
-            batch = self._assemble(h)
+            batch = self._assemble_resident(h) if h.get("resident") else self._assemble(h)
         self._stream.synchronize()          # the staging set is rewritten prefetch + 2 batches later; the host waits for THIS stream only
+        if h.get("resident"):
+            batch = self._settle_resident(h, batch)
         user = torch.cuda.current_stream()
         for t in batch:
             t.record_stream(user)
+        return batch
+
+    def _settle_resident(self, h, batch):
+        """After the synchronisation: a clean decode commits the batch's new images to the pool's dictionary; a flagged job gives their
+        stretches back and redoes the whole batch on the host path (same images, same tables), which produces it or raises its own message."""
+        if not h["status"].numpy().any():
+            self._resident.commit(h["entries"])
+            self.stats["decoded_images"] += len(h["fresh"])
+            self.stats["resident_hits"] += len(h["known"])
+            self.stats["scratch_images"] += h["scratch_images"]
+            return batch
+        self._resident.rollback(h["mark"])
+        self.stats["host_fallback_batches"] += 1
+        hs = self.stager.stage(h["order"], h["which"])
+        assert np.array_equal(hs["n"], h["n"]) and np.array_equal(hs["wh"], h["wh"])
+        h.update(Rcap=hs["Rcap"], src=hs["src"], stage=hs["stage"], staged_all=hs["staged_all"])
+        with torch.cuda.stream(self._stream):
+            batch = self._assemble(h)
+        self._stream.synchronize()
         return batch
 
     def _index_batches(self):
@@ -987,9 +1237,10 @@ class TaskLoader:
 
     def _staged_batches(self):
         nsets = len(self.stager._sets)
+        stage = self._stage_resident if self._resident is not None else self._stage
         if not self.prefetch:
             for k, idx in enumerate(self._index_batches()):
-                yield self._stage(idx, k % nsets)
+                yield stage(idx, k % nsets)
             return
         q, stop = queue.Queue(maxsize=self.prefetch), threading.Event()
 
@@ -1005,7 +1256,7 @@ class TaskLoader:
         def fill():
             try:
                 for k, idx in enumerate(self._index_batches()):
-                    if not put(self._stage(idx, k % nsets)):
+                    if not put(stage(idx, k % nsets)):
                         return
                 put(None)
             except BaseException as e:      # handed to the consumer, raised there

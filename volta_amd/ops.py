@@ -269,6 +269,104 @@ def task_batch(feat, boxes, n, wh, segs, mask_count, R, num_locs, add_global, sc
     return out
 
 
+def _pool_args(regions, where, feat_off, box_off, mean_off, n, wh, F, add_global):
+    """the slot half of vk_task_pool_args: regions = (pool, scratch) uint8 device tensors (None = empty), per-slot tables on the device"""
+    S = n.shape[0]
+    for t, dt, shape in ((where, torch.int32, (S,)), (feat_off, torch.int64, (S,)), (box_off, torch.int64, (S,)), (n, torch.int32, (S,)), (wh, torch.int32, (S, 2))):
+        assert t.is_cuda and t.dtype == dt and tuple(t.shape) == shape and t.is_contiguous(), (t.dtype, tuple(t.shape), shape)
+    assert len(regions) == 2 and F % 4 == 0 and F > 0 and add_global in GLOBAL_CODE
+    a = L.TaskPoolArgs()
+    for w, r in enumerate(regions):
+        if r is not None and r.numel():
+            assert r.is_cuda and r.dtype == torch.uint8 and r.is_contiguous() and r.data_ptr() % 16 == 0
+            a.base[w], a.bytes[w] = r.data_ptr(), r.numel()
+    a.where, a.feat_off, a.box_off, a.n, a.wh = ptr(where), ptr(feat_off), ptr(box_off), ptr(n), ptr(wh)
+    if mean_off is not None:
+        assert mean_off.is_cuda and mean_off.dtype == torch.int64 and tuple(mean_off.shape) == (S,) and mean_off.is_contiguous()
+        a.mean_off = ptr(mean_off)
+    a.S, a.F, a.R, a.num_locs, a.add_global = S, F, 1, 4, GLOBAL_CODE[add_global]
+    a._refs = (regions, where, feat_off, box_off, mean_off, n, wh)
+    return a
+
+
+def task_pool_means(regions, where, feat_off, box_off, mean_off, n, wh, F, slots):
+    """vk_task_pool_means: the global row (rows added in order in fp32, one division by n) of the slots the int32 device list `slots` names,
+    written at their mean_off of region where[s].  Arguments as `task_batch_pool`."""
+    assert mean_off is not None and slots.is_cuda and slots.dtype == torch.int32 and slots.dim() == 1 and slots.is_contiguous()
+    a = _pool_args(regions, where, feat_off, box_off, mean_off, n, wh, F, "first")
+    check(L.lib.vk_task_pool_means(C.byref(a), ptr(slots), slots.numel(), stream_ptr()))
+
+
+def task_batch_pool(regions, where, feat_off, box_off, mean_off, n, wh, F, segs, mask_count, R, num_locs, add_global, scatter=None, ref_box=None,
+                    out=None):
+    """vk_task_batch_pool: `task_batch` over images kept in two byte regions.  regions = (pool, scratch) uint8 device tensors (either may be
+    None); slot s holds features [n[s], F] at byte feat_off[s], boxes [n[s], 4] at box_off[s] and its global row [F] at mean_off[s] (needed
+    when add_global is not None; written by `task_pool_means`) of region where[s] (int32 0 | 1; the offsets are int64 tensors).  Everything
+    else, and the returned dict, as `task_batch`.  The slot tables are checked on the device: a slot that fails contributes no row."""
+    dev = n.device
+    N = segs.shape[0]
+    for t, dt, shape in ((segs, torch.int32, (N, L.TASK_MAX_SEGS, 4)), (mask_count, torch.int32, (N,))):
+        assert t.is_cuda and t.dtype == dt and tuple(t.shape) == shape and t.is_contiguous(), (t.dtype, tuple(t.shape), shape)
+    assert num_locs in (4, 5) and R > 0 and (add_global is None or mean_off is not None)
+    assert scatter is None or ref_box is None
+    a = _pool_args(regions, where, feat_off, box_off, mean_off, n, wh, F, add_global)
+    out = dict(out) if out else {}
+
+    def buf(name, shape, dt):
+        t = out.get(name)
+        if t is None:
+            t = out[name] = torch.empty(shape, dtype=dt, device=dev)
+        assert t.is_cuda and t.dtype == dt and tuple(t.shape) == tuple(shape) and t.is_contiguous(), name
+        return t
+
+    features, spatials, image_mask = buf("features", (N, R, F), torch.float32), buf("spatials", (N, R, num_locs), torch.float32), buf("image_mask", (N, R), torch.int64)
+    a.segs, a.mask_count, a.features, a.spatials, a.image_mask = ptr(segs), ptr(mask_count), ptr(features), ptr(spatials), ptr(image_mask)
+    a.N, a.R, a.num_locs = N, R, num_locs
+    if scatter is not None:
+        csr, labels, scores, num_labels = scatter
+        B = csr.numel() - 1
+        assert csr.dtype == torch.int32 and labels.dtype == torch.int32 and scores.dtype == torch.float32 and csr.is_cuda and labels.is_cuda and scores.is_cuda
+        assert B >= 0 and labels.numel() == scores.numel() and num_labels > 0
+        target = buf("target", (B, num_labels), torch.float32)
+        a.target, a.csr, a.labels, a.scores, a.B, a.num_labels, a.target_kind = ptr(target), ptr(csr), ptr(labels), ptr(scores), B, num_labels, L.TASK_TARGET_SCATTER
+    elif ref_box is not None:
+        assert ref_box.is_cuda and ref_box.dtype == torch.float32 and tuple(ref_box.shape) == (N, 4) and ref_box.is_contiguous()
+        target = buf("target", (N, R, 1), torch.float32)
+        a.target, a.ref_box, a.target_kind = ptr(target), ptr(ref_box), L.TASK_TARGET_IOU
+    check(L.lib.vk_task_batch_pool(C.byref(a), stream_ptr()))
+    return out
+
+
+def b64_jobs(fields):
+    """fields: (text_off, dst_off, nsig, want_bytes) per job -> (the vk_b64_job table as an int32 host tensor [njobs, 6], max nsig).  Checks
+    from the lengths what the device would refuse: want_bytes a multiple of 4 and nsig * 3 // 4, 16-byte aligned offsets."""
+    import numpy as np
+    tab = np.zeros(len(fields), np.dtype([("text_off", "<u8"), ("dst_off", "<u8"), ("nsig", "<u4"), ("want_bytes", "<u4")]))
+    for j, (text_off, dst_off, nsig, want) in enumerate(fields):
+        if want % 4 or want != nsig * 3 // 4 or nsig >= 1 << 31:
+            raise ValueError("base64 job %d: %d characters do not decode to %d bytes of fp32" % (j, nsig, want))
+        if text_off % 16 or dst_off % 16:
+            raise ValueError("base64 job %d: offsets %d / %d are not 16-byte aligned" % (j, text_off, dst_off))
+        tab[j] = (text_off, dst_off, nsig, want)
+    return torch.from_numpy(tab.view(np.int32).reshape(len(fields), 6)), int(tab["nsig"].max()) if len(fields) else 0
+
+
+def b64_decode_device(text, dst, jobs, max_nsig, status=None):
+    """vk_b64_decode_device: `text` (uint8 device tensor, the packed text fields) decoded into `dst` (uint8 device tensor, or any contiguous
+    device tensor taken as bytes) as the job table says (`jobs`: int32 device tensor [njobs, 6] from `b64_jobs`).  Returns the status words as
+    an int32 device tensor [njobs] (view them as uint32 on the host): 0 decoded, 1 + offset of the first offending byte, 0xFFFFFFFE for a job
+    the device's table check refused."""
+    assert text.is_cuda and text.dtype == torch.uint8 and text.is_contiguous() and dst.is_cuda and dst.is_contiguous()
+    assert jobs.is_cuda and jobs.dtype == torch.int32 and jobs.dim() == 2 and jobs.shape[1] == 6 and jobs.is_contiguous()
+    njobs = jobs.shape[0]
+    if status is None:
+        status = torch.empty(njobs, dtype=torch.int32, device=jobs.device)
+    assert status.is_cuda and status.dtype == torch.int32 and status.numel() >= njobs and status.is_contiguous()
+    check(L.lib.vk_b64_decode_device(ptr(text), text.numel(), ptr(dst), dst.numel() * dst.element_size(), ptr(jobs), njobs, int(max_nsig), ptr(status),
+                                     stream_ptr()))
+    return status[:njobs]
+
+
 def _ranks_csr(caption_image, Ni):
     """the captions of each image as a CSR over the captions with a valid image (sort + counts; nothing here reads a value on the host)
     -> image_ptr int32 [Ni + 1], image_captions int32 [Nc]"""

@@ -88,7 +88,7 @@ def LoadDataset(args, config, task_cfg, task_id, split="trainval"):
     if args.local_rank != -1:
         batch_size = int(batch_size / world)
     seed = int(getattr(args, "seed", 0) or 0)
-    kw = dict(drop_last=args.drop_last, in_memory=args.in_memory, threads=_threads(args, world))
+    kw = dict(drop_last=args.drop_last, in_memory=args.in_memory, threads=_threads(args, world), resident_bytes=getattr(args, "resident_bytes", 0))
     dset_train, dl_train, task2num_iters = None, None, {}
     if "train" in split:
         dset_train = _dataset(D.DatasetMapTrain, args, config, cfg, readers, tokenizer, cfg["train_annotations_jsonpath"], cfg["train_split"])
@@ -121,7 +121,8 @@ def LoadDatasetEval(args, config, task_cfg, task_id):
         dl_val = D.RetrievalEvalLoader(dset_val)
         return batch_size, {task: len(dl_val)}, dset_val, dl_val
     dset_val = _dataset(D.DatasetMapEval, args, config, cfg, readers, tokenizer, cfg["val_annotations_jsonpath"], split)
-    dl_val = D.TaskLoader(dset_val, batch_size, None, drop_last=args.drop_last, in_memory=args.in_memory, threads=_threads(args, world))
+    dl_val = D.TaskLoader(dset_val, batch_size, None, drop_last=args.drop_last, in_memory=args.in_memory, threads=_threads(args, world),
+                          resident_bytes=getattr(args, "resident_bytes", 0))
     return batch_size, {task: len(dl_val)}, dset_val, dl_val
 
 
